@@ -5,6 +5,17 @@ on the 3-D Poisson matrix (examples/benchmark.cpp:353-477), 512^3 grid.
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: starts its N ranks itself,
                                                             and refuses when the box has fewer GPUs than ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                             (everything else this file measures or checks, see below)
+    python bench.py ... --dump-outputs DIR                 (y of the last timed step, sampled, as DIR/*.npy)
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line: metric, value, unit, ms_per_step,
+the roofline of the launched kernel from the timed steps' own events, and the configuration.  `--full` adds what takes
+work of its own: the in-run check against an independent evaluation, five blocks of K steps instead of one, the set-up
+record, the sustained run, device copies, rocprofv3 counter passes, the secondary rows, the CPU baseline and, for N > 1,
+the per-rank check and the C++ multi-device row.
+`--dump-outputs DIR` writes, right after the timed steps, y at a fixed sample of rows (2^21 draws of a fixed seed,
+sorted and without repeats; every row below that size) as DIR/y.npy and the row numbers as DIR/y_rows.npy, both float64.
+x is a hash of the global row index, so the inputs are the same in every run with the same arguments.
 
 One "step" = one product y = A*x through vex::SpMat's path: the C-ABI object `vexhip_spmat`
 (include/vexhip.h) that both front ends -- the C++ headers (vexcl/spmat.hpp) and the Python
@@ -18,24 +29,24 @@ What the line reports, and how to read it:
   value / csr_algorithmic_gbps   2*nnz / t and CSR-ALGORITHMIC bytes / t (nnz*12 + (N+1)*4 + 16*N):
                       the metric's own definition, independent of how the matrix is stored -- NOT an achieved HBM rate when the
                       storage is smaller than CSR (it exceeds the 8 TB/s peak then); the achieved rate is roofline.achieved.
-  ms_per_step         the MEDIAN of five blocks of K steps (median-of-5 of total / M), each block bracketed by a
-                      barrier + synchronize on both sides; block 1 is the driver's "W warm-ups, then exactly K steps"; all five,
-                      their minimum and maximum are under `blocks`.
+  ms_per_step         the MEDIAN of the blocks of K steps, each block bracketed by a barrier + synchronize on both sides: one block
+                      in a plain run (W warm-ups, then exactly K steps), five with --full (SURVEY 8(d): median-of-5 of total / M;
+                      block 1 is the plain run's); every block, their minimum and maximum are under `blocks`.
   roofline            the launched kernel against the HBM roofline by the bytes it REALLY moves: the stored matrix
-                      (vexhip_spmat_get_info: matrix_bytes) + x once + y once.  frac <= 1 by construction.  `traffic`
+                      (vexhip_spmat_get_info: matrix_bytes) + x once + y once.  frac <= 1 by construction.  --full: `traffic`
                       = HBM bytes per launch measured in THIS run (rocprofv3 FETCH_SIZE / WRITE_SIZE passes over
                       tools/pmc_headline.py, FETCH calibrated on a stream of known size), or null.  `device_copy_hand`
                       (plane / march product): x copied to y by a hand kernel (vexhip_stream_copy_f64: one 16-byte pair per
                       lane, non-temporal stores) in the same process -- the same HBM traffic as the product (x once, y once):
                       what the memory system gives a kernel with nothing else to do; `device_copy`: torch's copy of the same;
                       `frac_of_measured_copy` = hand copy time / product time.
-  roofline_csr        the same product by kernels that stream fp64 values + int32 columns (no compression), priced
+  roofline_csr        (--full) the same product by kernels that stream fp64 values + int32 columns (no compression), priced
                       with the CSR-algorithmic bytes: SELL-512 with 32-bit columns and the CSR arrays themselves.
-  variable_coefficient  the same 7-point pattern with a coefficient per face (~4 N distinct values: no value coding
+  variable_coefficient  (--full) the same 7-point pattern with a coefficient per face (~4 N distinct values: no value coding
                       applies) through the default SpMat: the general-matrix figure.
-  checksum            sum(y) asserted against an independent evaluation of the stencil (torch slicing, no matrix); for N > 1 every
+  checksum            (--full) sum(y) asserted against an independent evaluation of the stencil (torch slicing, no matrix); for N > 1 every
                       rank checks its rows against x regenerated from the global index (no transport involved).
-  setup               what building the storage from CSR arrays in HBM costs (ms, bytes, products to amortise it).
+  setup               (--full) what building the storage from CSR arrays in HBM costs (ms, bytes, products to amortise it).
 N > 1: rank 0 says on stderr where the run is ("[bench  12.3 s] ..."); the trial and settle runs of a transport are bounded
 in time by a three-product probe whose result all ranks share.
 """
@@ -207,13 +218,20 @@ def transports_by_time(tried):
     return timed + [k for k in tried if tried[k].get("valid") and k not in timed]
 
 
-def timed_events(torch, fn, reps):
-    """Average duration of fn over `reps` launches, after ~30 ms of the same launches: these rows run after host-side work
-    (matrix set-up, subprocesses), and after >= 5 ms without work the first ~16 ms of launches are up to 12 % slow."""
+def out_of_idle(torch, fn):
+    """~30 ms of fn's launches, queued: after >= 5 ms without work the first ~16 ms of launches are up to 12 % slow.
+    Returns the two events of the first launch."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); fn(); e1.record(); torch.cuda.synchronize()
     for _ in range(min(200, int(30.0 / max(e0.elapsed_time(e1), 0.05)))):
         fn()
+    return e0, e1
+
+
+def timed_events(torch, fn, reps):
+    """Average duration of fn over `reps` launches, after ~30 ms of the same launches: these rows run after host-side work
+    (matrix set-up, subprocesses)."""
+    e0, e1 = out_of_idle(torch, fn)
     e0.record()
     for _ in range(reps):
         fn()
@@ -535,6 +553,30 @@ def secondary_rows(torch, L, ops, dev, local_rank):
     return rows
 
 
+DUMP_ROWS = 1 << 21            # --dump-outputs: rows of y sampled (<= 2 x 16 MB of float64)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(torch, dist, y, r0, n_rows, world, rank, out_dir):
+    """--dump-outputs: y at a fixed sample of the global rows, gathered in row order (every rank holds a contiguous strip, in
+    rank order) -> out_dir/y.npy, and the sampled rows -> out_dir/y_rows.npy (float64: exact below 2^53)."""
+    import numpy as np
+    if n_rows <= DUMP_ROWS:
+        rows = np.arange(n_rows, dtype=np.int64)
+    else:
+        rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_rows, DUMP_ROWS, dtype=np.int64))
+    mine = rows[(rows >= r0) & (rows < r0 + y.numel())] - r0
+    vals = y[torch.from_numpy(mine).to(y.device)].double().cpu().numpy()
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, vals)
+        vals = np.concatenate(parts)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "y.npy"), vals)
+        np.save(os.path.join(out_dir, "y_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     # a flag wait of the peer-window transports gives up after 20 s by default (ranks of a job may be seconds apart); inside this bench every
     # product stands between barriers, so a flag that does not come within 5 s never comes: a transport that does not work on this
@@ -567,10 +609,16 @@ def main():
     ap.add_argument("--no-march", action="store_true", help="keep the pair product where the march / plane products would apply")
     ap.add_argument("--no-direct", action="store_true", help="build the SELL-512 storage (slices, dictionary, plans) where the default set-up stores the matrix by grid line (round 4)")
     ap.add_argument("--no-plane", action="store_true", help="keep the march product (x window in an LDS ring, round 3) where the plane product (round 4) would apply")
-    ap.add_argument("--blocks", type=int, default=5, help="blocks of K steps; ms_per_step is their median (block 1 = the W warm-ups + exactly K steps of the contract)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: in-run checks, five blocks, set-up record, sustained run, "
+                                                         "device copies, counter passes, secondary rows, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write y of the last timed step at a fixed sample of rows to DIR/y.npy (rows: DIR/y_rows.npy)")
+    ap.add_argument("--blocks", type=int, default=None, help="blocks of K steps (default 1, with --full 5); ms_per_step is their median "
+                                                             "(block 1 = the W warm-ups + exactly K steps of the contract)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the ~3 s back-to-back run of the product after the timed region")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 counter passes (roofline.traffic = null)")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args, sys.argv[1:])                      # does not return
@@ -630,9 +678,11 @@ def main():
         # its matrices (AMG set-up, a nonlinear iteration) pays this once per matrix.
         # The device is brought out of idle first (30 copies of x, ~12 ms): a set-up that follows a pause is clocked up to 5 ms slower
         # in its first kernel than one in the middle of a computation, which is where a solver rebuilds a matrix.
-        for _ in range(30):
-            y.copy_(x)
-        y.zero_()
+        # (only --full reports the set-up record, so only --full does this)
+        if args.full:
+            for _ in range(30):
+                y.copy_(x)
+            y.zero_()
         torch.cuda.synchronize()
         free0 = torch.cuda.mem_get_info(dev)[0]
         # (Python's cyclic collector is run NOW: a full collection over what `import torch` leaves behind takes ~40 ms, and whether
@@ -666,12 +716,13 @@ def main():
                  "stored_bytes": int(matrix_bytes),
                  "held_after_setup_bytes": int(free0 - torch.cuda.mem_get_info(dev)[0])}
         if storage not in ("csr",):
-            # a second creation on the same arrays: the set-up in the middle of a computation (every one-time cost of the process paid)
-            torch.cuda.synchronize(); ts1 = time.perf_counter()
-            A2 = ops.SpMat(ptr, col, val, fmt=args.format, dictionary=not args.no_dictionary, march=not args.no_march, plane=not args.no_plane, direct=not args.no_direct)
-            torch.cuda.synchronize()
-            setup["repeat_ms"] = round((time.perf_counter() - ts1) * 1e3, 3)
-            del A2
+            if args.full:
+                # a second creation on the same arrays: the set-up in the middle of a computation (every one-time cost of the process paid)
+                torch.cuda.synchronize(); ts1 = time.perf_counter()
+                A2 = ops.SpMat(ptr, col, val, fmt=args.format, dictionary=not args.no_dictionary, march=not args.no_march, plane=not args.no_plane, direct=not args.no_direct)
+                torch.cuda.synchronize()
+                setup["repeat_ms"] = round((time.perf_counter() - ts1) * 1e3, 3)
+                del A2
             del ptr, col, val                    # the product only needs the converted storage
             A.ptr = A.col = A.val = None
         step = lambda: A.apply(x, y, 1.0, False)
@@ -831,13 +882,16 @@ def main():
         return ((y - yref).abs().max(), yref.sum(dtype=torch.float64), bound_dev)
 
     check_dev = None
-    if single:
+    if single and args.full:
         # The first evaluation only loads torch's kernels and fills its allocator's cache (both stall the host for
         # milliseconds at a time: the device drains); the second one, which is the check, then runs without a gap.
         step()
         queue_check()
         step()
         check_dev = queue_check()
+    elif single:
+        # a plain run has no check: ~30 ms of the product itself bring the device out of idle ahead of the warm-up instead
+        out_of_idle(torch, step)
 
     # N > 1: the set-up above (partition exchange plan, validation of the C++ step) ends in host-side waits; the same 200
     # products on every rank bring the devices out of the post-idle transient before the W warm-ups (reported as settle_steps)
@@ -884,8 +938,10 @@ def main():
         block_wall = [float(v) for v in t]
     order = sorted(range(len(block_wall)), key=lambda i: block_wall[i])
     mid = order[len(order) // 2]
+    if args.dump_outputs:
+        dump_outputs(torch, dist, y, r0, N, world, rank, args.dump_outputs)
 
-    checksum = DistReductor("SUM_Kahan")(y)          # sum(y): the same for every N up to rounding
+    checksum = DistReductor("SUM_Kahan")(y) if args.full else None         # sum(y): the same for every N up to rounding
     elapsed = block_wall[mid]
     per_step = elapsed / args.steps
     kern_s = block_kern[mid] / 1e3 / args.steps   # average launch duration of the product on this rank in the median block (HIP events)
@@ -893,7 +949,7 @@ def main():
 
     check = None
     dist_extra = None
-    if not single:
+    if not single and args.full:
         # the y of the timed steps against the independent evaluation, then the slowest rank's phases
         d = (y - y_ind).abs()
         row_ok = bool((d <= tol_ind).all())
@@ -923,7 +979,7 @@ def main():
                       "step_ms_what": "median of 7 products with HIP events on both streams (vexhip_dist_spmv_profile): total, local part, wait "
                                       "for the ghosts after the local part, remote part; pack and exchange run beside the local part",
                       "transports_tried": tried, "transport_chosen": chosen, "rccl": A.rccl_info()}
-    if single:
+    if single and args.full:
         err, sum_ref, bound = (float(v) for v in check_dev)
         tol = 1e-10 * bound
         check = {"sum_y": checksum, "sum_y_independent": sum_ref, "max_abs_err": err,
@@ -934,7 +990,7 @@ def main():
     # ---- the same product launched back to back for ~3 s: a cross-check of the K-step figure against a long run (and GPU
     #      activity an outside sampler of the device can see; the timed region above lasts K x 0.8 ms)
     sustained = None
-    if single and not args.no_sustained:
+    if single and args.full and not args.no_sustained:
         nsoak = min(6000, max(args.steps, int(3.0 / per_step)))
         L.event_record(local_rank, e0, stream)
         for _ in range(nsoak):
@@ -947,6 +1003,8 @@ def main():
                      "gflops": round(2.0 * nnz_total / (ms2.value / nsoak) / 1e6, 1),
                      "what": "the same product launched back to back after the timed region (HIP events on the launch stream)"}
 
+    if not args.full:
+        setup = None                                 # (the set-up record is --full's)
     if setup is not None:
         setup["products_to_amortise"] = round(setup["setup_ms"] / (per_step * 1e3), 1)
     if rank == 0:
@@ -971,12 +1029,11 @@ def main():
             "dtype": "f64",
             "data": "synthetic",
             "front_end": "vexcl_amd/ops.py SpMat -> vexhip_spmat_create / vexhip_spmat_apply_f64 (the C++ vex::SpMat calls the same two; "
-                         "its own timing of this product is under secondary['C++ front end'])",
+                         "its own timing of this product is under secondary['C++ front end'] with --full)",
             "blocks": {"what": "blocks of K steps, each between barrier + synchronize; ms_per_step is the median block; block 1 = W warm-ups then exactly K steps",
                        "ms_per_step": [round(w / args.steps * 1e3, 5) for w in block_wall],
                        "min": round(min(block_wall) / args.steps * 1e3, 5), "max": round(max(block_wall) / args.steps * 1e3, 5),
                        "event_ms_per_step": [round(k / args.steps, 5) for k in block_kern]},
-            "checksum": check if check else {"sum_y": checksum},
             "csr_algorithmic_gbps": round(gbps, 1),
             "csr_algorithmic_gbps_note": "CSR-algorithmic bytes / time (the metric's definition, SURVEY 8(d)); NOT an HBM rate when the storage is "
                                          "smaller than CSR -- the bytes the kernel moves and its achieved rate are under roofline",
@@ -1009,6 +1066,8 @@ def main():
                          "traffic": None,
                          "avg_launch_ms": round(kern_s * 1e3, 5)},
         }
+        if check:
+            out["checksum"] = check
         if setup is not None:
             out["setup"] = setup
         if world > 1:
@@ -1042,25 +1101,26 @@ def main():
                             "with four workgroups per CU the memory system is saturated (profiles/r03_sq_summary_march_v8.txt, DESIGN.md 3.0b)",
                     "bytes_per_launch": l1_bytes, "achieved": round(l1_bytes / kern_s / 1e9, 1), "peak_l2": 34500.0, "unit": "GB/s",
                     "frac_of_l2": round(l1_bytes / kern_s / 1e9 / 34500.0, 4)}
-            try:
-                yc = torch.empty_like(x)
-                copies = {"device_copy": ("torch's copy of x to y on this device, same process: the same HBM traffic as the product (x once, y once)",
-                                          lambda: yc.copy_(x)),
-                          "device_copy_hand": ("vexhip_stream_copy_f64: x copied to y with one 16-byte pair per lane and non-temporal stores, same process -- "
-                                               "the ceiling the memory system gives a kernel that moves these bytes and does nothing else",
-                                               lambda: L.stream_copy_f64(local_rank, stream, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(yc.data_ptr()), x.numel()))}
-                for name, (what, fn) in copies.items():
-                    copy_ms = min(timed_events(torch, fn, 20) for _ in range(3))
-                    out["roofline"][name] = {"what": what, "ms": round(copy_ms, 5), "gbps": round(2 * x.numel() * x.element_size() / copy_ms / 1e6, 1),
-                                             "frac_of_8TBps": round(2 * x.numel() * x.element_size() / copy_ms / 1e6 / HBM_PEAK_GBPS, 4),
-                                             "copy_over_product": round(copy_ms / 1e3 / kern_s, 4)}
-                assert torch.equal(yc, x), "vexhip_stream_copy_f64 does not copy"
-                out["roofline"]["frac_of_measured_copy"] = out["roofline"]["device_copy_hand"]["copy_over_product"]
-                del yc
-            except AssertionError:
-                raise
-            except Exception as e:  # noqa: BLE001 -- a comparison, not the measurement
-                out["roofline"]["device_copy"] = {"error": str(e)[:200]}
+            if args.full:                   # copies of x timed beside the product
+                try:
+                    yc = torch.empty_like(x)
+                    copies = {"device_copy": ("torch's copy of x to y on this device, same process: the same HBM traffic as the product (x once, y once)",
+                                              lambda: yc.copy_(x)),
+                              "device_copy_hand": ("vexhip_stream_copy_f64: x copied to y with one 16-byte pair per lane and non-temporal stores, same process -- "
+                                                   "the ceiling the memory system gives a kernel that moves these bytes and does nothing else",
+                                                   lambda: L.stream_copy_f64(local_rank, stream, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(yc.data_ptr()), x.numel()))}
+                    for name, (what, fn) in copies.items():
+                        copy_ms = min(timed_events(torch, fn, 20) for _ in range(3))
+                        out["roofline"][name] = {"what": what, "ms": round(copy_ms, 5), "gbps": round(2 * x.numel() * x.element_size() / copy_ms / 1e6, 1),
+                                                 "frac_of_8TBps": round(2 * x.numel() * x.element_size() / copy_ms / 1e6 / HBM_PEAK_GBPS, 4),
+                                                 "copy_over_product": round(copy_ms / 1e3 / kern_s, 4)}
+                    assert torch.equal(yc, x), "vexhip_stream_copy_f64 does not copy"
+                    out["roofline"]["frac_of_measured_copy"] = out["roofline"]["device_copy_hand"]["copy_over_product"]
+                    del yc
+                except AssertionError:
+                    raise
+                except Exception as e:  # noqa: BLE001 -- a comparison, not the measurement
+                    out["roofline"]["device_copy"] = {"error": str(e)[:200]}
         elif storage == "sell8v" and dict_blocks:
             # not HBM-bound any more: what the kernel pulls through L1 per product (ELL width 7: seven 16-byte x gathers per
             # lane and row pair = 56 B/row, 16 B/row of codes from the pooled blocks, 8 B/row stored), against the L2 rate
@@ -1078,8 +1138,9 @@ def main():
             out["config"]["exchange_transport"] = transport
             out["config"]["backend"] = args.backend
             out["config"]["one_device_debug"] = bool(args.one_device)
-            out["distributed"] = dist_extra
-        if single and not args.no_secondary:
+            if dist_extra:
+                out["distributed"] = dist_extra
+        if single and args.full and not args.no_secondary:
             sec = {}
             try:
                 # ---- round 6: the product with a vector added in the same pass (vexhip_spmat_apply_axpby_f64): y = x + 2 A x takes x from the
@@ -1257,7 +1318,7 @@ def main():
                 sec["error"] = repr(e)
             out["secondary"] = sec
         A = None
-        if single and not args.no_pmc:
+        if single and args.full and not args.no_pmc:
             torch.cuda.empty_cache()
             try:
                 tr, how = measure_traffic(n)
@@ -1277,12 +1338,12 @@ def main():
                     out["roofline"]["traffic_read_written"] = [tr[key]["read"], tr[key]["written"]]
                     out["roofline"]["traffic_over_bytes_per_launch"] = round(tr[key]["total"] / float(moved_rank), 4)
                 out["roofline"]["traffic_all_kernels"] = tr
-        if single and not args.no_cpu_baseline:
+        if single and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_grid, args.cpu_seconds)
     # N > 1: north_star's own multi-GPU shape -- ONE vex::Context driving all N GPUs through the C++ headers (vexcl/spmat.hpp
     # built from per-device strips, vexcl/exchange.hpp) -- timed by rank 0 in a child process while the ranks of this job wait
     # at a barrier with their devices idle; reported next to the one-process-per-GPU figure, never part of it.
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         torch.cuda.synchronize()
         barrier()
         if rank == 0:
