@@ -170,22 +170,26 @@ static size_t clamp_index(size_t n, size_t i, long shift) {
     return std::min<size_t>(n - 1, std::max<long>(0, static_cast<long>(i) + shift));
 }
 
+// T = double keeps the reference's tolerances; for float they scale by the ratio of the types' epsilons (the host sum is in double either way)
+template <class T>
 static void check_stencil(size_t n, size_t width, int center) {
-    std::vector<double> s = random_vector<double>(width);
-    vex::stencil<double> S(ctx, s, center);
-    std::vector<double> x = random_vector<double>(n);
-    vex::vector<double> X(ctx, x), Y(ctx, n);
-    auto conv = [&](size_t i) { double sum = 0; long k = -center; for (size_t j = 0; j < s.size(); ++j, ++k) sum += s[j] * x[clamp_index(n, i, k)]; return sum; };
+    const double eps = std::numeric_limits<T>::epsilon() / std::numeric_limits<double>::epsilon();
+    std::vector<T> s = random_vector<T>(width);
+    vex::stencil<T> S(ctx, s, center);
+    std::vector<T> x = random_vector<T>(n);
+    vex::vector<T> X(ctx, x), Y(ctx, n);
+    auto conv = [&](size_t i) { double sum = 0; long k = -center; for (size_t j = 0; j < s.size(); ++j, ++k) sum += double(s[j]) * double(x[clamp_index(n, i, k)]); return sum; };
     Y = 1; Y += X * S;                                               // stencil.cpp:33-45
-    std::vector<double> got(n); vex::copy(Y, got);
-    for (size_t i = 0; i < n; ++i) CHECK_CLOSE(got[i], 1 + conv(i), 1e-8);
+    std::vector<T> got(n); vex::copy(Y, got);
+    for (size_t i = 0; i < n; ++i) CHECK_CLOSE(got[i], 1 + conv(i), 1e-8 * eps);
     Y = 42 * (X * S);                                                // :47-56
     vex::copy(Y, got);
-    for (size_t i = 0; i < n; ++i) CHECK_CLOSE(got[i], 42 * conv(i), 1e-8);
+    for (size_t i = 0; i < n; ++i) CHECK_CLOSE(got[i], 42 * conv(i), 1e-8 * eps);
     Y = X - S * X;                                                   // mixed with a vector term, either operand order
     vex::copy(Y, got);
-    for (size_t i = 0; i < n; i += 7) CHECK_SMALL(got[i] - (x[i] - conv(i)), 1e-10 * width);
+    for (size_t i = 0; i < n; i += 7) CHECK_SMALL(got[i] - (x[i] - conv(i)), 1e-10 * eps * width);
 }
+static void check_stencil(size_t n, size_t width, int center) { check_stencil<double>(n, width, center); }
 
 TEST_CASE(stencil_convolution) {
     check_stencil(1024, 1, 0);
@@ -198,6 +202,12 @@ TEST_CASE(stencil_convolution) {
     check_stencil(1001, 5, 2);                                       // sizes that are not multiples of the 4 outputs a lane folds
     check_stencil(4099, 21, 10);
     check_stencil(2050, 2, 1);
+}
+
+TEST_CASE(stencil_convolution_float) {                               // the float kernel on random data: a wrong neighbour shows
+    check_stencil<float>(1024, 3, 1);
+    check_stencil<float>(4099, 21, 10);
+    check_stencil<float>(1 << 20, 33, 16);
 }
 
 TEST_CASE(stencil_small_vector_and_two_stencils) {                   // stencil.cpp:59-110

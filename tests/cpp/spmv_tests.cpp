@@ -486,6 +486,43 @@ TEST_CASE(spmv_ccsr_irregular_operators) {                          // beyond th
     }
 }
 
+// The operators of (b) above in the value type T: with fewer than 32768 rows the class keeps its own kernel
+// (vexhip_spmv_ccsr_f64 / _f32) by default, a larger one is handed to vexhip_spmat.  Same host loop, summed in T; the
+// tolerance of the double cases scaled by the type's epsilon.
+template <class T>
+static void check_ccsr_operator(size_t N, int far) {
+    const double eps = std::numeric_limits<T>::epsilon() / std::numeric_limits<double>::epsilon();
+    std::vector<vex::command_queue> q1(1, ctx.queue(0));
+    std::vector<size_t> idx, row = {0, 1, 6, 9};
+    std::vector<int> col = {0, -far, -700, -2, 0, 5, 0, 1, far};
+    std::vector<T> val = {1, 0.5, -0.25, 2, 3, -1, 7, 0.125, -0.75};
+    for (size_t i = 0; i < N; ++i) idx.push_back(i < (size_t)far || i + far >= N ? 0 : (i % 5 == 0 ? 2 : 1));
+    vex::SpMatCCSR<T, int> A(q1[0], N, row.size() - 1, idx.data(), row.data(), col.data(), val.data());
+    std::vector<T> x = random_vector<T>(N), y0 = random_vector<T>(N), want(N), a(N), b(N);
+    for (size_t i = 0; i < N; ++i) {
+        T s = 0;
+        for (size_t j = row[idx[i]]; j < row[idx[i] + 1]; ++j) s += val[j] * x[i + col[j]];
+        want[i] = s;
+    }
+    vex::vector<T> X(q1, x), Y(q1, N);
+    Y = A * X; vex::copy(Y, b);
+    vex::vector<T> Y2(q1, N);
+    Y2 = T(1) * (A * X) + T(0) * X;                                  // the same product inside a fused kernel
+    vex::copy(Y2, a);
+    for (size_t i = 0; i < N; i += 5) CHECK_CLOSE(double(a[i]) + 100, double(b[i]) + 100, 1e-10 * eps);
+    for (size_t i = 0; i < N; ++i) CHECK_CLOSE(double(b[i]) + 100, double(want[i]) + 100, 1e-10 * eps);
+    vex::copy(y0, Y);
+    Y -= T(0.5) * (A * X);                                           // scaled, appended
+    vex::copy(Y, b);
+    for (size_t i = 0; i < N; ++i) CHECK_CLOSE(double(b[i]) + 100, double(y0[i]) - 0.5 * double(want[i]) + 100, 1e-10 * eps);
+}
+
+TEST_CASE(spmv_ccsr_small_and_float_operators) {
+    check_ccsr_operator<double>(20011, 3000);                        // N < 32768: the class's own kernel
+    check_ccsr_operator<float>(20011, 3000);
+    check_ccsr_operator<float>(100003, 40000);                       // float, large: handed to vexhip_spmat (f32)
+}
+
 TEST_CASE(spmv_inline_single_queue) {                                // spmv.cpp:233-260
     const size_t n = 1024;
     std::vector<vex::command_queue> queue(1, ctx.queue(0));

@@ -117,6 +117,19 @@ def test_cpp_reductor_order_modes(order):
     assert "0 failures" in out.stdout
 
 
+@pytest.mark.gpu
+def test_cpp_ccsr_keeps_its_own_kernel():
+    """VEXCL_CCSR_KERNEL=1: vex::SpMatCCSR hands nothing to vexhip_spmat, so every SpMatCCSR assertion of spmv_tests (the
+    Poisson operator of the reference, the irregular, small and float operators) must hold on the hand-written kernel
+    vexhip_spmv_ccsr_f64 / _f32 -- the product the class keeps for small operators, operators of 2^31 entries or more,
+    columns outside [0, n) and after an out-of-memory in the hand-over."""
+    exe = _build("spmv_tests")
+    env = dict(os.environ, VEXCL_CCSR_KERNEL="1")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
+    assert out.returncode == 0, out.stdout[-6000:] + out.stderr[-3000:]
+    assert "0 failures" in out.stdout
+
+
 def test_by_key_wave_scan_on_dpp_matches_the_shuffle_form():
     """Host model of the by-key wave scan (vexcl/scan_by_key.hpp): the DPP steps (VEXCL_SBK_DPP=1: row_shr 1/2/4/8, row_bcast:15,
     row_bcast:31) give every live lane the sum the six shuffle steps give it, on random head / live patterns (tools/r04_sbk_dpp_sim.py)."""
