@@ -799,6 +799,69 @@ def test_product_with_a_vector_added_is_bit_identical(T, oracle, built_lib):
             assert np.array_equal(dy.cpu().numpy(), f32(beta) * y0 + ax), (product, alpha, beta, "z = y")
 
 
+def _axpby_placements(T, oracle, A, ptr, col, val, what):
+    """y = alpha A x + beta z with z an array of its own, z = x and z = y, bit for bit against round(beta z_i) + oracle.spmv_csr(.., alpha)_i
+    in the matrix's value type."""
+    m = len(ptr) - 1
+    vt = val.dtype.type
+    x, z, y0 = (oracle.random_f64(seed, m).astype(vt) for seed in (11, 12, 13))
+    dx = T.up(x)
+    for alpha, beta in ((1.0, 1.0), (-1.0, 1.0), (0.5, -0.25)):
+        ax = oracle.spmv_csr(ptr, col, val, x, alpha=alpha)
+        dy = T.up(np.full(m, np.nan, dtype=vt)); A.apply_axpby(dx, dy, alpha, T.up(z), beta)
+        assert np.array_equal(dy.cpu().numpy(), vt(beta) * z + ax), (what, alpha, beta, "z")
+        dy = T.up(np.full(m, np.nan, dtype=vt)); A.apply_axpby(dx, dy, alpha, dx, beta)
+        assert np.array_equal(dy.cpu().numpy(), vt(beta) * x + ax), (what, alpha, beta, "z = x")
+        dy = T.up(y0); A.apply_axpby(dx, dy, alpha, dy, beta)
+        assert np.array_equal(dy.cpu().numpy(), vt(beta) * y0 + ax), (what, alpha, beta, "z = y")
+
+
+def _fused(T, built_lib, A, m):
+    v = T.torch.zeros(m, dtype=A.dtype, device=T.dev)
+    return bool(built_lib.spmat_axpby_fused(A.handle, T.ops._p(v), T.ops._p(v), T.ops._p(T.torch.zeros_like(v))))
+
+
+def test_vector_added_csr_with_64bit_row_pointers(T, oracle, built_lib):
+    """The addend through the CSR product of a matrix with 64-bit row pointers (the launcher takes it as an argument)."""
+    ptr, col, val = _grid7_natural(512, 6, 8)
+    A = T.ops.SpMat(T.up(ptr.astype(np.int64)), T.up(col), T.up(val), fmt="csr")
+    assert A.product == "csr_stream2_kernel" and "64-bit row pointers" in A.reason, (A.product, A.reason)
+    assert _fused(T, built_lib, A, len(ptr) - 1)
+    _axpby_placements(T, oracle, A, ptr, col, val, "csr, 64-bit row pointers")
+
+
+@pytest.mark.parametrize("ptr_type", [np.int32, np.int64])
+def test_vector_added_csr_unaligned_arrays(T, oracle, built_lib, ptr_type):
+    """Borrowed CSR arrays that start one element into an allocation are not 16-byte aligned: the one-row-per-lane CSR kernel adds the vector."""
+    ptr, col, val = _grid7_natural(512, 6, 8)
+    pad_c = T.up(np.concatenate([[0], col]).astype(np.int32))[1:]
+    pad_v = T.up(np.concatenate([[0.0], val]))[1:]
+    assert T.ops._p(pad_c).value % 16 != 0 and T.ops._p(pad_v).value % 16 != 0
+    A = T.ops.SpMat(T.up(ptr.astype(ptr_type)), pad_c, pad_v, fmt="csr")
+    assert A.storage == "csr" and _fused(T, built_lib, A, len(ptr) - 1)
+    _axpby_placements(T, oracle, A, ptr, col, val, ("csr, unaligned", ptr_type.__name__))
+
+
+@pytest.mark.parametrize("fmt", ["sell32", "sell8", "sell"])
+def test_vector_added_hybrid_matrix_with_a_csr_tail(T, oracle, built_lib, fmt):
+    """Rows wider than the ELL width keep a CSR tail: the kernels add the vector after the tail, in the same store."""
+    ptr, col, val = oracle.random_matrix(33, 1500, 1500, 16)           # (the matrix of test_sell_layout_and_tail)
+    A = T.ops.SpMat(T.up(ptr), T.up(col), T.up(val), fmt=fmt)
+    assert int(A.info.tail_nnz) > 0 and A.storage != "csr", (A.storage, A.reason)
+    assert _fused(T, built_lib, A, len(ptr) - 1)
+    _axpby_placements(T, oracle, A, ptr, col, val, (fmt, A.product))
+
+
+@pytest.mark.parametrize("fmt,kw", [("csr", {}), ("sell32", {}), ("sell8", {}), ("sell", {"march": False})])
+def test_vector_added_float_store_pair_storages(T, oracle, built_lib, fmt, kw):
+    """Float matrices in the storages whose kernels add the vector in their store: every rounding is a float's."""
+    ptr, col, val = _grid7_natural(64, 16, 16)
+    v32 = val.astype(np.float32)
+    A = T.ops.SpMat(T.up(ptr), T.up(col), T.up(v32), fmt=fmt, **kw)
+    assert A.dtype == T.torch.float32 and _fused(T, built_lib, A, len(ptr) - 1), (A.product, A.reason)
+    _axpby_placements(T, oracle, A, ptr, col, v32, (fmt, A.product))
+
+
 def test_grid_product_fp32_is_bit_identical(T, oracle, built_lib):
     """The fp32 grid product (round 5, grid32.hip: the walk of the fp64 grid product with FOUR rows per lane -- 16-byte requests at
     4-byte addresses, the lane at the end of a line stores 1 .. 3 rows) against the pair product and the fp32 CSR restatement,

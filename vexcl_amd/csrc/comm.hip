@@ -12,6 +12,7 @@
 // librccl is loaded on first use (dlopen): a single-GPU user of libvexhip.so never pays for it.
 #include "common.hpp"
 #include "halo.hpp"
+#include "storage.hpp"
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -22,13 +23,6 @@
 #include <new>
 #include <vector>
 
-namespace vexhip {
-// spmat.hip: the stored strip of a rank as the operand of the one-launch step (halo.hpp)
-int spmat_halo_geometry(const vexhip_spmat *h, int *planes, int *lines_per_plane, int *line_length, int *value_type);
-int spmat_halo_general(const vexhip_spmat *h, int64_t halo, int64_t rows_ext, int *reach, int *value_type);
-int spmat_device(const vexhip_spmat *h, int *dev);
-int spmat_apply_halo(const vexhip_spmat *h, hipStream_t s, double alpha, int append, const void *x, void *y, const halo_dev &H);
-}
 namespace vexhip {
 namespace {
 

@@ -107,6 +107,11 @@ struct setup_trace {
     }
 };
 
+// scan.hip: the scans that other files of the library run inside their own steps
+int scan_exclusive_i32_internal(int dev, hipStream_t s, const int *in, int *out, int64_t n);
+int scan_exclusive_u32_tmp(hipStream_t s, const unsigned *in, unsigned *out, int64_t n, unsigned *tmp);
+size_t scan_tmp_elems_u32(int64_t n);
+
 } // namespace vexhip
 
 #define VEXHIP_TRY(expr)                                                      \

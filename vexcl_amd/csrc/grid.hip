@@ -29,6 +29,7 @@
 #include "halo.hpp"
 #include "lanes.hpp"
 #include "grid.hpp"
+#include "storage.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -978,12 +979,14 @@ template <typename T> struct dev_buf {       // device scratch of the plan, free
 };
 
 
+} // namespace
+
 // ---- host side of the direct build ----
 // rows x rows-or-more matrix in CSR on the device -> vexhip_grid (usable = 1), the diagonal table (sorted, 256 ints on the device,
 // INT_MAX behind the last) and the value table (256 values on the device, 0.0 behind the last), ELL width and largest column;
 // usable = 0: not a matrix for this storage, nothing was written that the classic set-up would read.
 // fp32 (V = float): the same tables; the products are plane32.hip (512-point lines) and grid32.hip (any line length).
-template <typename P, typename V>
+template <typename V, typename P>
 int grid_build(int dev, void *stream, int64_t rows, const P *ptr, const int32_t *col, const V *val,
         int32_t *deltas, V *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last_out, vexhip_grid *out, int64_t min_cols)
 {
@@ -1088,30 +1091,13 @@ int grid_build(int dev, void *stream, int64_t rows, const P *ptr, const int32_t 
     return 0;
 }
 
-} // namespace
-
-// internal entry points of the direct build (spmat.hip)
-int grid_build_p32(int dev, void *stream, int64_t rows, const int32_t *ptr, const int32_t *col, const double *val,
-        int32_t *deltas, double *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols)
-{ return grid_build<int32_t, double>(dev, stream, rows, ptr, col, val, deltas, values, ndeltas, nvalues, ell_width, x_last, out, min_cols); }
-int grid_build_p64(int dev, void *stream, int64_t rows, const long long *ptr, const int32_t *col, const double *val,
-        int32_t *deltas, double *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols)
-{ return grid_build<long long, double>(dev, stream, rows, ptr, col, val, deltas, values, ndeltas, nvalues, ell_width, x_last, out, min_cols); }
-int grid_build_p32(int dev, void *stream, int64_t rows, const int32_t *ptr, const int32_t *col, const float *val,
-        int32_t *deltas, float *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols)
-{ return grid_build<int32_t, float>(dev, stream, rows, ptr, col, val, deltas, values, ndeltas, nvalues, ell_width, x_last, out, min_cols); }
-int grid_build_p64(int dev, void *stream, int64_t rows, const long long *ptr, const int32_t *col, const float *val,
-        int32_t *deltas, float *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols)
-{ return grid_build<long long, float>(dev, stream, rows, ptr, col, val, deltas, values, ndeltas, nvalues, ell_width, x_last, out, min_cols); }
+#define VEXHIP_INSTANTIATE(V, P) template int grid_build<V, P>(int, void *, int64_t, const P *, const int32_t *, const V *, int32_t *, V *, int *, int *, int64_t *, int64_t *, vexhip_grid *, int64_t);
+VEXHIP_INSTANTIATE(double, int32_t) VEXHIP_INSTANTIATE(double, long long) VEXHIP_INSTANTIATE(float, int32_t) VEXHIP_INSTANTIATE(float, long long)
+#undef VEXHIP_INSTANTIATE
 
 } // namespace vexhip
 
 using namespace vexhip;
-
-namespace vexhip {
-int grid_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, const double *values,
-        const double *x, double *y, const vexhip_grid *g);
-}
 
 extern "C" {
 
@@ -1242,9 +1228,7 @@ int vexhip_sell8_grid_check(const vexhip_grid *g, int64_t n)
 
 int vexhip_spmv_sell8v_grid_f64(int dev, void *stream, int64_t n, double alpha, int append, const double *values,
         const double *x, double *y, const vexhip_grid *g)
-{
-    return grid_apply_axpby(dev, stream, n, alpha, append ? 1 : 0, y, 1.0, values, x, y, g);
-}
+{ return grid_apply<double>(dev, stream, n, alpha, append, values, x, y, g); }
 
 } // extern "C"
 

@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "lanes.hpp"
 #include "grid.hpp"
+#include "storage.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -277,24 +278,17 @@ void sell8_grid_f32_kernel(const float *__restrict__ x, float *__restrict__ y, f
 
 using namespace vexhip;
 
-namespace vexhip {
-int grid32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, const float *values,
-        const float *x, float *y, const vexhip_grid *g);
-}
-
 extern "C" {
 
 int vexhip_spmv_sell8v_grid_f32(int dev, void *stream, int64_t n, float alpha, int append, const float *values,
         const float *x, float *y, const vexhip_grid *g)
-{
-    return grid32_apply_axpby(dev, stream, n, alpha, append ? 1 : 0, y, 1.0f, values, x, y, g);
-}
+{ return grid_apply<float>(dev, stream, n, alpha, append, values, x, y, g); }
 
 } // extern "C"
 
 namespace vexhip {
 // y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the fp32 grid product (spmat.hip vexhip_spmat_apply_axpby_f32)
-int grid32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, const float *values,
+int grid_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, const float *values,
         const float *x, float *y, const vexhip_grid *g)
 {
     VEXHIP_REQUIRE(g && g->usable && g->line_class && g->table && values && x && y, "bad grid product arguments");

@@ -3,15 +3,12 @@
 // built directly in HBM (examples/benchmark.cpp:364-415), and fills.
 // None of this is on the timed path.
 #include "common.hpp"
+#include "storage.hpp"
 
 #include <algorithm>
 #include <vector>
 
 namespace vexhip {
-
-// scan.hip
-int scan_exclusive_i32_internal(int dev, hipStream_t s, const int *in, int *out, int64_t n);
-
 namespace {
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
@@ -205,6 +202,9 @@ inline int grid_for(int dev, int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)info(dev).cus * 16));
 }
 
+} // namespace
+
+// ---- the hybrid-ELL rule and fill (storage.hpp) ----
 template <typename V, typename P>
 int hell_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, const V *val,
         int64_t w, int64_t pitch, int *ell_col, V *ell_val, int *csr_ptr, int *csr_col, V *csr_val)
@@ -279,16 +279,12 @@ int hell_analyze(int dev, void *stream, int64_t n, const P *ptr,
     return 0;
 }
 
-
-} // namespace
-
-// 64-bit row pointers: internal entry points for spmat.hip (the tail CSR keeps 32-bit pointers: it must stay below 2^31 entries)
-int hell_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, int64_t *ell_width, int64_t *tail_nnz)
-{ return hell_analyze<long long>(dev, stream, n, ptr, ell_width, tail_nnz); }
-int hell_tail_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, int32_t *csr_ptr, int32_t *csr_col, double *csr_val)
-{ return hell_fill<double, long long>(dev, stream, n, ptr, col, val, w, (n + 15) / 16 * 16, nullptr, nullptr, csr_ptr, csr_col, csr_val); }
-int hell_tail_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, int32_t *csr_ptr, int32_t *csr_col, float *csr_val)
-{ return hell_fill<float, long long>(dev, stream, n, ptr, col, val, w, (n + 15) / 16 * 16, nullptr, nullptr, csr_ptr, csr_col, csr_val); }
+// 64-bit row pointers: the tail CSR keeps 32-bit pointers (it must stay below 2^31 entries)
+template int hell_analyze<int32_t>(int, void *, int64_t, const int32_t *, int64_t *, int64_t *);
+template int hell_analyze<long long>(int, void *, int64_t, const long long *, int64_t *, int64_t *);
+#define VEXHIP_INSTANTIATE(V, P) template int hell_fill<V, P>(int, void *, int64_t, const P *, const int *, const V *, int64_t, int64_t, int *, V *, int *, int *, V *);
+VEXHIP_INSTANTIATE(double, int32_t) VEXHIP_INSTANTIATE(float, int32_t) VEXHIP_INSTANTIATE(double, long long) VEXHIP_INSTANTIATE(float, long long)
+#undef VEXHIP_INSTANTIATE
 
 } // namespace vexhip
 

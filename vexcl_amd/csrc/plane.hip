@@ -28,6 +28,7 @@
 #include "lanes.hpp"
 #include "halo.hpp"
 #include "plane.hpp"
+#include "storage.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -768,9 +769,7 @@ int vexhip_sell8_plane_plan(int dev, void *stream, const int32_t *deltas, int nd
 
 int vexhip_spmv_sell8v_plane_f64_i32(int dev, void *stream, int64_t n, double alpha, int append, int64_t w, const void *pool,
         const int32_t *blocks, const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane)
-{
-    return plane_apply_axpby(dev, stream, n, alpha, append ? 1 : 0, y, 1.0, w, pool, blocks, deltas, values, x, y, plane);
-}
+{ return plane_apply<double>(dev, stream, n, alpha, append, w, pool, blocks, deltas, values, x, y, plane); }
 
 int vexhip_stream_copy_f64(int dev, void *stream, const double *x, double *y, int64_t n)
 {

@@ -13,6 +13,7 @@
 #include "halo.hpp"
 #include "lanes.hpp"
 #include "plane.hpp"
+#include "storage.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -335,11 +336,6 @@ void sell8_plane_f32_kernel(const float *__restrict__ x, float *__restrict__ y, 
 
 using namespace vexhip;
 
-namespace vexhip {
-int plane32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool,
-        const int32_t *blocks, const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane);
-}
-
 extern "C" {
 
 // Planes per workgroup of the fp32 plane product (host arithmetic only, exported so that the choice can be checked without a device):
@@ -361,15 +357,13 @@ int64_t vexhip_sell8_plane_f32_depth(int cus, int64_t lines_per_plane, int64_t p
 
 int vexhip_spmv_sell8v_plane_f32_i32(int dev, void *stream, int64_t n, float alpha, int append, int64_t w, const void *pool,
         const int32_t *blocks, const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane)
-{
-    return plane32_apply_axpby(dev, stream, n, alpha, append ? 1 : 0, y, 1.0f, w, pool, blocks, deltas, values, x, y, plane);
-}
+{ return plane_apply<float>(dev, stream, n, alpha, append, w, pool, blocks, deltas, values, x, y, plane); }
 
 } // extern "C"
 
 namespace vexhip {
 // y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the fp32 plane product (spmat.hip vexhip_spmat_apply_axpby_f32)
-int plane32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool,
+int plane_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool,
         const int32_t *blocks, const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane)
 {
     VEXHIP_REQUIRE(plane && plane->usable && pool && blocks && deltas && values && x && y, "bad plane product arguments");
@@ -409,7 +403,7 @@ int plane32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, c
 
 // One device's product step in one launch for a float matrix on 512-point lines (halo.hpp, the pull form): the fp32 plane product over
 // the planes [H.z0, H.z1) of the stored grid of n_ext rows; x and y are the device's own segments.
-int plane32_apply_halo(int dev, hipStream_t s, int64_t n_ext, float alpha, int append, int64_t w, const void *pool, const int32_t *blocks,
+int plane_apply_halo(int dev, hipStream_t s, int64_t n_ext, float alpha, int append, int64_t w, const void *pool, const int32_t *blocks,
         const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane, halo_dev H)
 {
     VEXHIP_REQUIRE(plane && plane->usable && pool && blocks && deltas && values && x && y, "bad plane product arguments");

@@ -19,6 +19,7 @@
 #include "traversal.hpp"
 #include "pairing.hpp"
 #include "halo.hpp"
+#include "storage.hpp"
 #include "lanes.hpp"
 
 #include <algorithm>
@@ -34,13 +35,9 @@ namespace vexhip {
 // 0 = pair kernels (one 16-byte gather per lane and column; default), 1 = one 8-byte gather per entry (round 1).
 // 2 = pair kernels even where the march kernel applies.
 int g_sell8_variant = 0;
-// largest column index of the ELL part seen by the last sell8 / sell8v fill on this thread (x holds at least that + 1 elements)
-thread_local long long g_fill_max_col = -1;
-// set by the fused analysis (below) for the fill that follows it on this thread: the largest ELL column is known, the fill
-// skips its own pass over the column indices
-thread_local long long g_max_col_hint = -1;
-thread_local const void *g_hint_ptr = nullptr;
-thread_local long long g_hint_n = -1;
+// vexhip_sell8_last_fill_max_col: the largest ELL column the last vexhip_sell8_fill_* / vexhip_sell8v_fill_* call on this thread stored
+// (written by those exported wrappers alone; inside the library the fills return it)
+thread_local int64_t g_fill_max_col = -1;
 
 namespace {
 
@@ -1548,7 +1545,7 @@ inline long long march_lds_bytes(int lo, int hi, int value_bytes) {
 template <typename V>
 int march_launch(int dev, hipStream_t s, int64_t n, long long ns, V alpha, int append, int w, const int *deltas, const V *values,
         const int *cp, const int *cc, const V *cv, const V *x, V *y, const vexhip_traversal *tr, const char *pool, const int *blocks,
-        const vexhip_march *m)
+        const vexhip_march *m, addend add)
 {
     VEXHIP_REQUIRE(m->lo <= 0 && m->hi >= 0 && m->run >= 1 && m->nfar >= 0 && m->nfar <= 2, "bad march plan");
     const bool strips = tr && tr->grid_blocks > 0 && tr->chunk > 0;
@@ -1557,7 +1554,7 @@ int march_launch(int dev, hipStream_t s, int64_t n, long long ns, V alpha, int a
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     trav_dev t8 = {nullptr, 0, 0, 0};
     if (strips) t8 = trav_dev{nullptr, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
-    t8 = with_addend(t8);                                                  // y = alpha A x + beta z: the kernel is told by append == 2
+    t8 = attach(t8, add);                                                  // y = alpha A x + beta z: the kernel is told by append == 2
     if (t8.z) append = 2;
     const int lo_e = m->lo & ~1;                                           // window bounds on even elements (16-byte ring accesses)
     const long long span_b = march_span_bytes(m->lo, m->hi, (int)sizeof(V));
@@ -1621,9 +1618,12 @@ void strip_traversal(int64_t n, const std::vector<int> &table, const std::vector
     if (out->grid_blocks >= (1ll << 31)) std::memset(out, 0, sizeof(*out));
 }
 
+} // namespace
+
+// ---- the typed set-up steps and products (storage.hpp) ----
 template <typename V, typename P>
 int sell8_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, const V *val, int64_t w,
-        const int *deltas, int ndeltas, void *buf, vexhip_traversal *trav)
+        const int *deltas, int ndeltas, void *buf, vexhip_traversal *trav, int64_t known_max_col, int64_t *max_col)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 1 && ndeltas >= 1 && ndeltas <= 254, "bad SELL8 geometry");
     if (trav) std::memset(trav, 0, sizeof(*trav));
@@ -1636,9 +1636,8 @@ int sell8_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, c
     VEXHIP_TRY(hipMalloc(&dcounts, sizeof(unsigned long long) * 256 + 4 * sizeof(int)));
     int *dinfo = reinterpret_cast<int *>(dcounts + 256);                    // [0] unused, [1] error flag, [2] largest ELL column
     VEXHIP_TRY(hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * 256 + 2 * sizeof(int), s));
-    if (g_max_col_hint >= 0 && g_hint_ptr == static_cast<const void *>(ptr) && g_hint_n == n) {   // the fused analysis of THIS matrix ran just before on this thread
-        const int known = (int)g_max_col_hint;
-        g_max_col_hint = -1;
+    if (known_max_col >= 0) {                                               // (the fused analysis of this matrix found it)
+        const int known = (int)known_max_col;
         VEXHIP_TRY(hipMemcpyAsync(dinfo + 2, &known, sizeof(int), hipMemcpyHostToDevice, s));
         VEXHIP_TRY(hipStreamSynchronize(s));
     } else {
@@ -1659,7 +1658,7 @@ int sell8_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, c
     VEXHIP_TRY(hipMemcpyAsync(table.data(), deltas, sizeof(int) * ndeltas, hipMemcpyDeviceToHost, s));
     VEXHIP_TRY(hipStreamSynchronize(s));
     VEXHIP_TRY(hipFree(dcounts));
-    g_fill_max_col = hinfo[2];
+    if (max_col) *max_col = hinfo[2];
     VEXHIP_REQUIRE(hinfo[1] == 0, "SELL8 fill: the matrix uses a diagonal that is not in the table");
     if (trav) strip_traversal(n, table, counts, trav);
     return 0;
@@ -1668,7 +1667,7 @@ int sell8_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, c
 template <typename V>
 int spmv_sell8(int dev, void *stream, int64_t n, V alpha, int append, int64_t w, const void *buf, const int *deltas,
         const int *cp, const int *cc, const V *cv, const V *x, V *y, const vexhip_traversal *tr,
-        const void *pool_ = nullptr, const int *blocks = nullptr)
+        const void *pool_, const int *blocks, addend add)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 1 && w < (1 << 20), "bad SELL8 geometry");
     if (n == 0) return 0;
@@ -1681,7 +1680,7 @@ int spmv_sell8(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
     const long long grid = ordered ? tr->grid_blocks : ns;
     trav_dev t8 = {nullptr, 0, 0, 0};
     if (ordered) t8 = trav_dev{tr->order, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
-    t8 = with_addend(t8);                                          // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
+    t8 = attach(t8, add);                                          // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     const char *b = static_cast<const char *>(buf), *pool = static_cast<const char *>(pool_);
 #define PAIR(W, DICT) sell8_pair_kernel<V, W, false, DICT><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, b, deltas, (const V *)nullptr, cp, cc, cv, x, y, t8, pool, blocks)
@@ -1734,10 +1733,10 @@ int sell8v_analyze(int dev, void *stream, int64_t n, const P *ptr, const V *val,
 // deltas[256] / values[256]: device tables as the two separate analyses write them; *ndeltas / *nvalues = -1 when not applicable
 template <typename V, typename P>
 int analyze_fused(int dev, void *stream, int64_t n, const P *ptr, const int *col, const V *val, int64_t w,
-        int32_t *deltas, int *ndeltas, V *values, int *nvalues)
+        int32_t *deltas, int *ndeltas, V *values, int *nvalues, int64_t *max_col)
 {
     typedef typename bits_of<V>::type B;
-    *ndeltas = -1; *nvalues = -1; g_max_col_hint = -1;
+    *ndeltas = -1; *nvalues = -1; *max_col = -1;
     if (n <= 0 || w < 1) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
@@ -1774,7 +1773,7 @@ int analyze_fused(int dev, void *stream, int64_t n, const P *ptr, const int *col
     (void)hipFree(d);
     trace.mark("  fused: hipFree");
     VEXHIP_TRY(e);
-    g_max_col_hint = hmax; g_hint_ptr = ptr; g_hint_n = n;
+    *max_col = hmax;
     if (!(hd[HASH_SLOTS + 1] != 0 || hd[HASH_SLOTS] > 254 || hd[HASH_SLOTS] < 1)) {
         std::vector<int> table;
         for (int k = 0; k < HASH_SLOTS; ++k) if (hd[k] != EMPTY) table.push_back(hd[k]);
@@ -1801,7 +1800,7 @@ int analyze_fused(int dev, void *stream, int64_t n, const P *ptr, const int *col
 
 template <typename V, typename P>
 int sell8v_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, const V *val, int64_t w,
-        const int *deltas, int ndeltas, const V *values, int nvalues, void *buf, vexhip_traversal *trav)
+        const int *deltas, int ndeltas, const V *values, int nvalues, void *buf, vexhip_traversal *trav, int64_t known_max_col, int64_t *max_col)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 1 && ndeltas >= 1 && ndeltas <= 254 && nvalues >= 1 && nvalues <= 255, "bad SELL8V geometry");
     if (trav) std::memset(trav, 0, sizeof(*trav));
@@ -1814,9 +1813,8 @@ int sell8v_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, 
     VEXHIP_TRY(hipMalloc(&dcounts, sizeof(unsigned long long) * 256 + 4 * sizeof(int)));
     int *dinfo = reinterpret_cast<int *>(dcounts + 256);                    // [0] unused, [1] error flag, [2] largest ELL column
     VEXHIP_TRY(hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * 256 + 2 * sizeof(int), s));
-    if (g_max_col_hint >= 0 && g_hint_ptr == static_cast<const void *>(ptr) && g_hint_n == n) {   // the fused analysis of THIS matrix ran just before on this thread
-        const int known = (int)g_max_col_hint;
-        g_max_col_hint = -1;
+    if (known_max_col >= 0) {                                               // (the fused analysis of this matrix found it)
+        const int known = (int)known_max_col;
         VEXHIP_TRY(hipMemcpyAsync(dinfo + 2, &known, sizeof(int), hipMemcpyHostToDevice, s));
         VEXHIP_TRY(hipStreamSynchronize(s));
     } else {
@@ -1837,7 +1835,7 @@ int sell8v_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, 
     VEXHIP_TRY(hipMemcpyAsync(table.data(), deltas, sizeof(int) * ndeltas, hipMemcpyDeviceToHost, s));
     VEXHIP_TRY(hipStreamSynchronize(s));
     VEXHIP_TRY(hipFree(dcounts));
-    g_fill_max_col = hinfo[2];
+    if (max_col) *max_col = hinfo[2];
     VEXHIP_REQUIRE(hinfo[1] == 0, "SELL8V fill: a diagonal or a value of the matrix is not in its table");
     if (trav) strip_traversal(n, table, counts, trav);
     return 0;
@@ -1845,8 +1843,8 @@ int sell8v_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, 
 
 template <typename V>
 int spmv_sell8v(int dev, void *stream, int64_t n, V alpha, int append, int64_t w, const void *buf, const int *deltas, const V *values,
-        const int *cp, const int *cc, const V *cv, const V *x, V *y, const vexhip_traversal *tr, const int *blocks = nullptr,
-        const vexhip_march *march = nullptr)
+        const int *cp, const int *cc, const V *cv, const V *x, V *y, const vexhip_traversal *tr, const int *blocks,
+        const vexhip_march *march, addend add)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 1 && w < (1 << 20), "bad SELL8V geometry");
     if (n == 0) return 0;
@@ -1859,8 +1857,8 @@ int spmv_sell8v(int dev, void *stream, int64_t n, V alpha, int append, int64_t w
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     const char *b = static_cast<const char *>(buf);
     if (march && blocks && w <= 8 && g_sell8_variant == 0 && !(tr && tr->order))
-        return march_launch<V>(dev, s, n, ns, alpha, append, (int)w, deltas, values, cp, cc, cv, x, y, tr, b, blocks, march);
-    t8 = with_addend(t8);
+        return march_launch<V>(dev, s, n, ns, alpha, append, (int)w, deltas, values, cp, cc, cv, x, y, tr, b, blocks, march, add);
+    t8 = attach(t8, add);
 #define PAIRV(W, DICT) sell8_pair_kernel<V, (W <= 8 ? W : 8), true, DICT><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, b, deltas, values, cp, cc, cv, x, y, t8, b, blocks)
 #define CASE(W) case W: if (g_sell8_variant != 1 && W <= 8) { if (blocks) PAIRV(W, true); else PAIRV(W, false); } \
         else sell8v_kernel<V, W><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, x, y, t8, blocks); break;
@@ -1886,6 +1884,7 @@ int spmv_sell8v(int dev, void *stream, int64_t n, V alpha, int append, int64_t w
 // bit-identical.  Measured before it was built (profiles/r02_sell8v_ablation.json: every slice reading one of 8 fixed
 // blocks): 0.764 -> 0.641 ms with cached loads, 0.808 ms with the non-temporal loads of the streamed layout.
 // ---------------------------------------------------------------------------
+namespace {
 __global__ __launch_bounds__(256)
 void slice_hash_kernel(long long nslices, long long stride_words, long long slice_words, const unsigned *__restrict__ buf, unsigned long long *__restrict__ hash)
 {
@@ -1927,6 +1926,8 @@ void slice_pool_kernel(long long stride_words, long long slice_words, const unsi
     unsigned *o = pool + (long long)blockIdx.x * slice_words;
     for (long long k = threadIdx.x; k < slice_words; k += 256) o[k] = a[k];
 }
+
+} // namespace
 
 int slice_dictionary(int dev, void *stream, int64_t nslices, int64_t stride_bytes, int64_t slice_bytes, const void *buf, int64_t max_blocks,
         int32_t *blocks, void *pool, int64_t *nblocks)
@@ -2022,9 +2023,6 @@ int sell8_analyze(int dev, void *stream, int64_t n, const P *ptr, const int32_t 
     return 0;
 }
 
-
-} // namespace
-
 int sell8_apply_halo(int dev, hipStream_t s, long long own_rows, double alpha, int append, int w, bool vcoded, const void *buf, const void *pool,
         const int *blocks, const int *deltas, const double *values, const double *x, double *y, halo_dev H)
 { return sell8_apply_halo_impl<double>(dev, s, own_rows, alpha, append, w, vcoded, buf, pool, blocks, deltas, values, x, y, H); }
@@ -2032,7 +2030,7 @@ int sell8_apply_halo(int dev, hipStream_t s, long long own_rows, double alpha, i
 // ---- runs of three diagonals (above): the plan of a dictionary's blocks, and the product (spmat.hip) ----
 // desc_out: device array of nblocks x 4 waves x RUNS_STRIDE ints (hipFree), NULL when no wave of any block holds a fast group
 template <typename V>
-static int sell8v_runs_plan_impl(int dev, void *stream, const void *pool, int64_t nblocks, int64_t w, const int *deltas, const V *values, int **desc_out)
+int sell8v_runs_plan(int dev, void *stream, const void *pool, int64_t nblocks, int64_t w, const int *deltas, const V *values, int **desc_out)
 {
     VEXHIP_REQUIRE(desc_out, "NULL output");
     *desc_out = nullptr;
@@ -2056,14 +2054,11 @@ static int sell8v_runs_plan_impl(int dev, void *stream, const void *pool, int64_
     *desc_out = desc;
     return 0;
 }
-int sell8v_runs_plan(int dev, void *stream, const void *pool, int64_t nblocks, int64_t w, const int *deltas, const double *values, int **desc_out)
-{ return sell8v_runs_plan_impl<double>(dev, stream, pool, nblocks, w, deltas, values, desc_out); }
-int sell8v_runs_plan(int dev, void *stream, const void *pool, int64_t nblocks, int64_t w, const int *deltas, const float *values, int **desc_out)
-{ return sell8v_runs_plan_impl<float>(dev, stream, pool, nblocks, w, deltas, values, desc_out); }
 
 template <typename V>
-static int sell8v_runs_apply_impl(int dev, void *stream, int64_t n, V alpha, int append, int64_t w, const void *pool, const int *blocks,
-        const int *deltas, const V *values, const int *cp, const int *cc, const V *cv, const V *x, V *y, const vexhip_traversal *tr, const int *desc, long long x_last)
+int sell8v_runs_apply(int dev, void *stream, int64_t n, V alpha, int append, int64_t w, const void *pool, const int *blocks,
+        const int *deltas, const V *values, const int *cp, const int *cc, const V *cv, const V *x, V *y, const vexhip_traversal *tr, const int *desc, long long x_last,
+        addend add)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 10 && w <= 3 * RUNS_GROUPS && pool && blocks && deltas && values && desc && x_last >= 0, "bad arguments of the runs product");
     if (n == 0) return 0;
@@ -2075,53 +2070,14 @@ static int sell8v_runs_apply_impl(int dev, void *stream, int64_t n, V alpha, int
     trav_dev t8 = make_traversal(tr, ns, &grid);
     if (!t8.order && t8.chunk == 0) grid = 8 * ((ns + 7) / 8);                        // (the kernel deals the slices to the XCDs itself)
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-    t8 = with_addend(t8);
+    t8 = attach(t8, add);
     sell8v_runs_kernel<V><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, static_cast<const char *>(pool), deltas, values, cp, cc, cv, x, y, t8, blocks, desc, x_last);
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
-int sell8v_runs_apply(int dev, void *stream, int64_t n, double alpha, int append, int64_t w, const void *pool, const int *blocks, const int *deltas, const double *values,
-        const int *cp, const int *cc, const double *cv, const double *x, double *y, const vexhip_traversal *tr, const int *desc, long long x_last)
-{ return sell8v_runs_apply_impl<double>(dev, stream, n, alpha, append, w, pool, blocks, deltas, values, cp, cc, cv, x, y, tr, desc, x_last); }
-int sell8v_runs_apply(int dev, void *stream, int64_t n, float alpha, int append, int64_t w, const void *pool, const int *blocks, const int *deltas, const float *values,
-        const int *cp, const int *cc, const float *cv, const float *x, float *y, const vexhip_traversal *tr, const int *desc, long long x_last)
-{ return sell8v_runs_apply_impl<float>(dev, stream, n, alpha, append, w, pool, blocks, deltas, values, cp, cc, cv, x, y, tr, desc, x_last); }
-
-
-// ---- 64-bit row pointers (a device may hold 2^31 entries or more; columns stay 32-bit): internal entry points used by
-//      spmat.hip -- vexhip_spmat_create_*_p64 is the C-ABI door (reference: size_t row pointers, vexcl/spmat.hpp:56-57)
-int analyze_fused_p32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const double *val, int64_t w, int32_t *deltas, int *ndeltas, double *values, int *nvalues)
-{ return analyze_fused<double, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues); }
-int analyze_fused_p32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const float *val, int64_t w, int32_t *deltas, int *ndeltas, float *values, int *nvalues)
-{ return analyze_fused<float, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues); }
-int analyze_fused_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, int32_t *deltas, int *ndeltas, double *values, int *nvalues)
-{ return analyze_fused<double, long long>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues); }
-int analyze_fused_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, int32_t *deltas, int *ndeltas, float *values, int *nvalues)
-{ return analyze_fused<float, long long>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues); }
-void clear_max_col_hint() { g_max_col_hint = -1; g_hint_ptr = nullptr; g_hint_n = -1; }
-// the largest ELL column the fused analysis of THIS matrix saw on this thread (-1: no such analysis): the direct grid build (grid.hip)
-long long analysis_max_col(const void *ptr, long long n) { return (g_max_col_hint >= 0 && g_hint_ptr == ptr && g_hint_n == n) ? g_max_col_hint : -1; }
-int sell8_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, int64_t w, int32_t *deltas, int *ndeltas)
-{ return sell8_analyze<long long>(dev, stream, n, ptr, col, w, deltas, ndeltas); }
-int sell8v_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, const double *val, int64_t w, double *values, int *nvalues)
-{ return sell8v_analyze<double, long long>(dev, stream, n, ptr, val, w, values, nvalues); }
-int sell8v_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, const float *val, int64_t w, float *values, int *nvalues)
-{ return sell8v_analyze<float, long long>(dev, stream, n, ptr, val, w, values, nvalues); }
-int sell8v_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w,
-        const int32_t *deltas, int ndeltas, const double *values, int nvalues, void *buf, vexhip_traversal *trav)
-{ return sell8v_fill<double, long long>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues, buf, trav); }
-int sell8v_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w,
-        const int32_t *deltas, int ndeltas, const float *values, int nvalues, void *buf, vexhip_traversal *trav)
-{ return sell8v_fill<float, long long>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues, buf, trav); }
-int sell8_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w,
-        const int32_t *deltas, int ndeltas, void *buf, vexhip_traversal *trav)
-{ return sell8_fill<double, long long>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, buf, trav); }
-int sell8_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w,
-        const int32_t *deltas, int ndeltas, void *buf, vexhip_traversal *trav)
-{ return sell8_fill<float, long long>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, buf, trav); }
 
 template <typename P>
-int csr_traversal_impl(int dev, void *stream, int64_t n, const P *ptr, const int32_t *col,
+int csr_traversal(int dev, void *stream, int64_t n, const P *ptr, const int32_t *col,
         int rows_per_block, vexhip_traversal *traversal)
 {
     VEXHIP_REQUIRE(traversal && rows_per_block > 0, "bad argument");
@@ -2152,9 +2108,29 @@ int csr_traversal_impl(int dev, void *stream, int64_t n, const P *ptr, const int
     return rc;
 }
 
-// 64-bit row pointers: the strips of a CSR matrix kept in CSR with 2^31 entries or more (spmat.hip)
-int csr_traversal_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, int rows_per_block, vexhip_traversal *traversal)
-{ return csr_traversal_impl<long long>(dev, stream, n, ptr, col, rows_per_block, traversal); }
+// the combinations in use (64-bit row pointers: a device may hold 2^31 entries or more; columns stay 32-bit)
+#define VEXHIP_INSTANTIATE_P(P) \
+    template int sell8_analyze<P>(int, void *, int64_t, const P *, const int32_t *, int64_t, int32_t *, int *); \
+    template int csr_traversal<P>(int, void *, int64_t, const P *, const int32_t *, int, vexhip_traversal *);
+#define VEXHIP_INSTANTIATE_VP(V, P) \
+    template int sell8v_analyze<V, P>(int, void *, int64_t, const P *, const V *, int64_t, V *, int *); \
+    template int analyze_fused<V, P>(int, void *, int64_t, const P *, const int *, const V *, int64_t, int32_t *, int *, V *, int *, int64_t *); \
+    template int sell8v_fill<V, P>(int, void *, int64_t, const P *, const int *, const V *, int64_t, const int *, int, const V *, int, void *, vexhip_traversal *, int64_t, int64_t *); \
+    template int sell8_fill<V, P>(int, void *, int64_t, const P *, const int *, const V *, int64_t, const int *, int, void *, vexhip_traversal *, int64_t, int64_t *);
+#define VEXHIP_INSTANTIATE_V(V) \
+    VEXHIP_INSTANTIATE_VP(V, int32_t) VEXHIP_INSTANTIATE_VP(V, long long) \
+    template int sell8v_runs_plan<V>(int, void *, const void *, int64_t, int64_t, const int *, const V *, int **); \
+    template int sell8v_runs_apply<V>(int, void *, int64_t, V, int, int64_t, const void *, const int *, const int *, const V *, const int *, const int *, const V *, const V *, V *, \
+            const vexhip_traversal *, const int *, long long, addend); \
+    template int spmv_sell8<V>(int, void *, int64_t, V, int, int64_t, const void *, const int *, const int *, const int *, const V *, const V *, V *, const vexhip_traversal *, \
+            const void *, const int *, addend); \
+    template int spmv_sell8v<V>(int, void *, int64_t, V, int, int64_t, const void *, const int *, const V *, const int *, const int *, const V *, const V *, V *, \
+            const vexhip_traversal *, const int *, const vexhip_march *, addend);
+VEXHIP_INSTANTIATE_P(int32_t) VEXHIP_INSTANTIATE_P(long long)
+VEXHIP_INSTANTIATE_V(double) VEXHIP_INSTANTIATE_V(float)
+#undef VEXHIP_INSTANTIATE_V
+#undef VEXHIP_INSTANTIATE_VP
+#undef VEXHIP_INSTANTIATE_P
 
 } // namespace vexhip
 
@@ -2181,10 +2157,10 @@ int vexhip_sell8v_analyze_f32_i32(int dev, void *stream, int64_t n, const int32_
 
 int vexhip_sell8v_fill_f64_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const double *val, int64_t w,
         const int32_t *deltas, int ndeltas, const double *values, int nvalues, void *buf, vexhip_traversal *traversal)
-{ return sell8v_fill<double, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues, buf, traversal); }
+{ return sell8v_fill<double, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues, buf, traversal, -1, &g_fill_max_col); }
 int vexhip_sell8v_fill_f32_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const float *val, int64_t w,
         const int32_t *deltas, int ndeltas, const float *values, int nvalues, void *buf, vexhip_traversal *traversal)
-{ return sell8v_fill<float, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues, buf, traversal); }
+{ return sell8v_fill<float, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, values, nvalues, buf, traversal, -1, &g_fill_max_col); }
 
 int vexhip_spmv_sell8v_f64_i32(int dev, void *stream, int64_t n, double alpha, int append, int64_t w, const void *buf,
         const int32_t *deltas, const double *values, const int32_t *cp, const int32_t *cc, const double *cv,
@@ -2282,15 +2258,15 @@ int vexhip_spmv_sell8v_march_f32_i32(int dev, void *stream, int64_t n, float alp
 { return spmv_sell8v<float>(dev, stream, n, alpha, append, w, pool, deltas, values, cp, cc, cv, x, y, traversal, blocks, (march && march->usable) ? march : nullptr); }
 int vexhip_csr_traversal_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col,
         int rows_per_block, vexhip_traversal *traversal)
-{ return csr_traversal_impl<int32_t>(dev, stream, n, ptr, col, rows_per_block, traversal); }
+{ return csr_traversal<int32_t>(dev, stream, n, ptr, col, rows_per_block, traversal); }
 
 int vexhip_sell8_fill_f64_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const double *val,
         int64_t w, const int32_t *deltas, int ndeltas, void *buf, vexhip_traversal *traversal)
-{ return sell8_fill<double, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, buf, traversal); }
+{ return sell8_fill<double, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, buf, traversal, -1, &g_fill_max_col); }
 
 int vexhip_sell8_fill_f32_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const float *val,
         int64_t w, const int32_t *deltas, int ndeltas, void *buf, vexhip_traversal *traversal)
-{ return sell8_fill<float, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, buf, traversal); }
+{ return sell8_fill<float, int32_t>(dev, stream, n, ptr, col, val, w, deltas, ndeltas, buf, traversal, -1, &g_fill_max_col); }
 
 int vexhip_spmv_sell8_f64_i32(int dev, void *stream, int64_t n, double alpha, int append, int64_t w,
         const void *buf, const int32_t *deltas, const int32_t *cp, const int32_t *cc, const double *cv,

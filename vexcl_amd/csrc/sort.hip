@@ -16,10 +16,6 @@
 #include <cstdlib>
 
 namespace vexhip {
-
-int scan_exclusive_u32_tmp(hipStream_t s, const unsigned *in, unsigned *out, int64_t n, unsigned *tmp);
-size_t scan_tmp_elems_u32(int64_t n);
-
 namespace {
 
 constexpr int RB = 1024;             // lanes per scatter workgroup (16 waves)

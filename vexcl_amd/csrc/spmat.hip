@@ -10,6 +10,7 @@
 // Both front ends now call create / apply / destroy.  Built from DEVICE CSR arrays: no host staging.
 #include "common.hpp"
 #include "halo.hpp"
+#include "storage.hpp"
 #include "traversal.hpp"
 
 #include <algorithm>
@@ -20,61 +21,6 @@
 #include <type_traits>
 
 namespace vexhip {
-
-// 64-bit row pointers (sell8.hip, spmv.hip, misc.hip): set-up and the CSR product for matrices with 2^31 entries or more
-int hell_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, int64_t *ell_width, int64_t *tail_nnz);
-int hell_tail_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, int32_t *csr_ptr, int32_t *csr_col, double *csr_val);
-int hell_tail_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, int32_t *csr_ptr, int32_t *csr_col, float *csr_val);
-int sell8_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, int64_t w, int32_t *deltas, int *ndeltas);
-void clear_max_col_hint();
-extern int g_sell8_variant;            // sell8.hip (vexhip_spmv_sell8_set_variant): 0 = default products
-// diagonals + values + largest ELL column in one pass over the CSR arrays (the fill that follows skips its own column pass)
-int analyze_fused_p32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const double *val, int64_t w, int32_t *deltas, int *ndeltas, double *values, int *nvalues);
-int analyze_fused_p32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const float *val, int64_t w, int32_t *deltas, int *ndeltas, float *values, int *nvalues);
-int analyze_fused_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, int32_t *deltas, int *ndeltas, double *values, int *nvalues);
-int analyze_fused_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, int32_t *deltas, int *ndeltas, float *values, int *nvalues);
-int sell8v_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, const double *val, int64_t w, double *values, int *nvalues);
-int sell8v_analyze_p64(int dev, void *stream, int64_t n, const long long *ptr, const float *val, int64_t w, float *values, int *nvalues);
-int sell8v_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, const int32_t *deltas, int ndeltas, const double *values, int nvalues, void *buf, vexhip_traversal *trav);
-int sell8v_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, const int32_t *deltas, int ndeltas, const float *values, int nvalues, void *buf, vexhip_traversal *trav);
-int sell8_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, const int32_t *deltas, int ndeltas, void *buf, vexhip_traversal *trav);
-int sell8_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, const int32_t *deltas, int ndeltas, void *buf, vexhip_traversal *trav);
-int sell_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, void *sell);
-int sell_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, void *sell);
-int spmv_csr_p64(int dev, void *stream, int64_t n, double alpha, int append, const long long *ptr, const int32_t *col, const double *val, const double *x, double *y, const vexhip_traversal *tr);
-int spmv_csr_p64(int dev, void *stream, int64_t n, float alpha, int append, const long long *ptr, const int32_t *col, const float *val, const float *x, float *y, const vexhip_traversal *tr);
-int csr_traversal_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, int rows_per_block, vexhip_traversal *traversal);
-int grid_build_p32(int dev, void *stream, int64_t rows, const int32_t *ptr, const int32_t *col, const double *val,
-        int32_t *deltas, double *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols);
-int grid_build_p64(int dev, void *stream, int64_t rows, const long long *ptr, const int32_t *col, const double *val,
-        int32_t *deltas, double *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols);
-int grid_build_p32(int dev, void *stream, int64_t rows, const int32_t *ptr, const int32_t *col, const float *val,
-        int32_t *deltas, float *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols);
-int grid_build_p64(int dev, void *stream, int64_t rows, const long long *ptr, const int32_t *col, const float *val,
-        int32_t *deltas, float *values, int *ndeltas, int *nvalues, int64_t *ell_width, int64_t *x_last, vexhip_grid *out, int64_t min_cols);
-int plane_plan_from_grid(int dev, const vexhip_grid *grid, int64_t rows, vexhip_plane *out);
-int plane_apply_halo(int dev, hipStream_t s, int64_t n_ext, double alpha, int append, int64_t w, const void *pool, const int32_t *blocks,
-        const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane, halo_dev H);
-int plane_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, int64_t w, const void *pool,
-        const int32_t *blocks, const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane);
-int grid_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, const double *values,
-        const double *x, double *y, const vexhip_grid *g);
-int plane32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool,
-        const int32_t *blocks, const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane);
-int grid32_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, const float *values,
-        const float *x, float *y, const vexhip_grid *g);
-int grid_apply_halo(int dev, hipStream_t s, int64_t n_ext, double alpha, int append, const double *values, const double *x, double *y,
-        const vexhip_grid *g, halo_dev H);
-int sell8v_runs_plan(int dev, void *stream, const void *pool, int64_t nblocks, int64_t w, const int *deltas, const double *values, int **desc_out);
-int sell8v_runs_plan(int dev, void *stream, const void *pool, int64_t nblocks, int64_t w, const int *deltas, const float *values, int **desc_out);
-int sell8v_runs_apply(int dev, void *stream, int64_t n, double alpha, int append, int64_t w, const void *pool, const int *blocks, const int *deltas, const double *values,
-        const int *cp, const int *cc, const double *cv, const double *x, double *y, const vexhip_traversal *tr, const int *desc, long long x_last);
-int sell8v_runs_apply(int dev, void *stream, int64_t n, float alpha, int append, int64_t w, const void *pool, const int *blocks, const int *deltas, const float *values,
-        const int *cp, const int *cc, const float *cv, const float *x, float *y, const vexhip_traversal *tr, const int *desc, long long x_last);
-int sell8_apply_halo(int dev, hipStream_t s, long long own_rows, double alpha, int append, int w, bool vcoded, const void *buf, const void *pool,
-        const int *blocks, const int *deltas, const double *values, const double *x, double *y, halo_dev H);
-int plane32_apply_halo(int dev, hipStream_t s, int64_t n_ext, float alpha, int append, int64_t w, const void *pool, const int32_t *blocks,
-        const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane, halo_dev H);
 
 namespace {
 
@@ -101,6 +47,12 @@ struct spmat {
     bool direct = false;                                           // stored by grid line straight from the CSR arrays (grid.hip grid_build): no SELL-512 slices, no dictionary
     char why[200] = {0};                                           // why this storage (the branch of build() that was taken)
 };
+
+// the class tables and the class of every line that the plane and grid products read: of the storage by grid line, or of the slice dictionary
+inline const void *tables(const spmat *A) { return A->direct ? A->grid.table : A->pool; }
+inline const int32_t *classes(const spmat *A) { return A->direct ? A->grid.line_class : A->blocks; }
+
+template <typename V> constexpr int value_type_of = std::is_same<V, double>::value ? VEXHIP_F64 : VEXHIP_F32;
 
 template <typename T> int dmalloc(T **p, size_t count) {
     *p = nullptr;
@@ -167,84 +119,34 @@ inline product_choice select_product(const spmat *A, const void *x, const void *
     }
 }
 
+// How the product that select_product chose takes the z of y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): in its walk (the plane and
+// grid products: from z, or -- z == x -- from the registers that hold x anyway), in its store (the launcher hands the addend to its kernels'
+// store_pair, traversal.hpp: the pair / any-width products of the coded storages and of the 32-bit columns, the CSR kernels and the march
+// product in their own epilogues), or not at all (y = beta z, then y += alpha A x).
+enum addend_route { ADD_NONE, ADD_WALK, ADD_STORE };
+inline bool addend_by_store_pair(product_kind k) {
+    return k == P_PAIR_CODES || k == P_PAIR_DICT_VALUES || k == P_PAIR_VALUES || k == P_SELL32 || k == P_MARCH || k == P_CSR32 || k == P_CSR64;
+}
+inline addend_route addend_route_of(product_kind k, const void *x, const void *z) {
+    switch (k) {
+        case P_PLANE64: return (z == x || (reinterpret_cast<uintptr_t>(z) & 15) == 0) ? ADD_WALK : ADD_NONE;
+        case P_GRID64: return (reinterpret_cast<uintptr_t>(z) & 7) == 0 ? ADD_WALK : ADD_NONE;
+        case P_PLANE32: case P_GRID32: return ADD_WALK;
+        default: return addend_by_store_pair(k) ? ADD_STORE : ADD_NONE;
+    }
+}
+
 template <typename V>
 __global__ __launch_bounds__(256) void scale_into_kernel(V *__restrict__ y, const V *z, V beta, long long n) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) y[i] = beta * z[i];                 // (z may be y itself)
 }
 
-template <typename V> struct api;
-template <> struct api<double> {
-    static constexpr int type = VEXHIP_F64;
-    static int hell_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const double *v, int64_t w, int64_t pitch, int32_t *cp, int32_t *cc, double *cv)
-    { return vexhip_hell_fill_f64_i32(d, s, n, p, c, v, w, pitch, nullptr, nullptr, cp, cc, cv); }
-    static int v_analyze(int d, void *s, int64_t n, const int32_t *p, const double *v, int64_t w, double *vals, int *nv) { return vexhip_sell8v_analyze_f64_i32(d, s, n, p, v, w, vals, nv); }
-    static int v_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const double *v, int64_t w, const int32_t *dl, int nd, const double *vals, int nv, void *b, vexhip_traversal *t)
-    { return vexhip_sell8v_fill_f64_i32(d, s, n, p, c, v, w, dl, nd, vals, nv, b, t); }
-    static int d_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const double *v, int64_t w, const int32_t *dl, int nd, void *b, vexhip_traversal *t)
-    { return vexhip_sell8_fill_f64_i32(d, s, n, p, c, v, w, dl, nd, b, t); }
-    static int s_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const double *v, int64_t w, void *b) { return vexhip_sell_fill_f64_i32(d, s, n, p, c, v, w, b); }
-    static int mul_v(int d, void *s, int64_t n, double a, int ap, int64_t w, const void *b, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const double *x, double *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell8v_f64_i32(d, s, n, a, ap, w, b, dl, (const double *)vals, cp, cc, (const double *)cv, x, y, t); }
-    static int mul_dd(int d, void *s, int64_t n, double a, int ap, int64_t w, const void *b, const void *pl, const int32_t *bl, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const double *x, double *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell8_dict_f64_i32(d, s, n, a, ap, w, b, pl, bl, dl, cp, cc, (const double *)cv, x, y, t); }
-    static int mm_dd(int d, void *s, int64_t n, int k, double a, int ap, int64_t w, const void *b, const void *pl, const int32_t *bl, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const double *const *x, double *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8_dict_f64_i32(d, s, n, k, a, ap, w, b, pl, bl, dl, cp, cc, (const double *)cv, x, y, t); }
-    static int mul_vd(int d, void *s, int64_t n, double a, int ap, int64_t w, const void *b, const int32_t *bl, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const double *x, double *y, const vexhip_traversal *t, const vexhip_march *m)
-    { return vexhip_spmv_sell8v_march_f64_i32(d, s, n, a, ap, w, b, bl, dl, (const double *)vals, cp, cc, (const double *)cv, x, y, t, m); }
-    static int mm_vd(int d, void *s, int64_t n, int k, double a, int ap, int64_t w, const void *b, const int32_t *bl, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const double *const *x, double *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8v_dict_f64_i32(d, s, n, k, a, ap, w, b, bl, dl, (const double *)vals, cp, cc, (const double *)cv, x, y, t); }
-    static int mul_d(int d, void *s, int64_t n, double a, int ap, int64_t w, const void *b, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const double *x, double *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell8_f64_i32(d, s, n, a, ap, w, b, dl, cp, cc, (const double *)cv, x, y, t); }
-    static int mul_s(int d, void *s, int64_t n, double a, int ap, int64_t w, const void *b, const int32_t *cp, const int32_t *cc, const void *cv, const double *x, double *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell_f64_i32(d, s, n, a, ap, w, b, cp, cc, (const double *)cv, x, y, t); }
-    static int mul_c(int d, void *s, int64_t n, double a, int ap, const int32_t *p, const int32_t *c, const void *v, const double *x, double *y, const vexhip_traversal *t)
-    { return vexhip_spmv_csr_ordered_f64_i32(d, s, n, a, ap, p, c, (const double *)v, x, y, t); }
-    static int mm_v(int d, void *s, int64_t n, int k, double a, int ap, int64_t w, const void *b, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const double *const *x, double *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8v_f64_i32(d, s, n, k, a, ap, w, b, dl, (const double *)vals, cp, cc, (const double *)cv, x, y, t); }
-    static int mm_d(int d, void *s, int64_t n, int k, double a, int ap, int64_t w, const void *b, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const double *const *x, double *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8_f64_i32(d, s, n, k, a, ap, w, b, dl, cp, cc, (const double *)cv, x, y, t); }
-    static int mm_s(int d, void *s, int64_t n, int k, double a, int ap, int64_t w, const void *b, const int32_t *cp, const int32_t *cc, const void *cv, const double *const *x, double *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell_f64_i32(d, s, n, k, a, ap, w, b, cp, cc, (const double *)cv, x, y, t); }
-};
-template <> struct api<float> {
-    static constexpr int type = VEXHIP_F32;
-    static int hell_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const float *v, int64_t w, int64_t pitch, int32_t *cp, int32_t *cc, float *cv)
-    { return vexhip_hell_fill_f32_i32(d, s, n, p, c, v, w, pitch, nullptr, nullptr, cp, cc, cv); }
-    static int v_analyze(int d, void *s, int64_t n, const int32_t *p, const float *v, int64_t w, float *vals, int *nv) { return vexhip_sell8v_analyze_f32_i32(d, s, n, p, v, w, vals, nv); }
-    static int v_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const float *v, int64_t w, const int32_t *dl, int nd, const float *vals, int nv, void *b, vexhip_traversal *t)
-    { return vexhip_sell8v_fill_f32_i32(d, s, n, p, c, v, w, dl, nd, vals, nv, b, t); }
-    static int d_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const float *v, int64_t w, const int32_t *dl, int nd, void *b, vexhip_traversal *t)
-    { return vexhip_sell8_fill_f32_i32(d, s, n, p, c, v, w, dl, nd, b, t); }
-    static int s_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const float *v, int64_t w, void *b) { return vexhip_sell_fill_f32_i32(d, s, n, p, c, v, w, b); }
-    static int mul_v(int d, void *s, int64_t n, float a, int ap, int64_t w, const void *b, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const float *x, float *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell8v_f32_i32(d, s, n, a, ap, w, b, dl, (const float *)vals, cp, cc, (const float *)cv, x, y, t); }
-    static int mul_dd(int d, void *s, int64_t n, float a, int ap, int64_t w, const void *b, const void *pl, const int32_t *bl, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const float *x, float *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell8_dict_f32_i32(d, s, n, a, ap, w, b, pl, bl, dl, cp, cc, (const float *)cv, x, y, t); }
-    static int mm_dd(int d, void *s, int64_t n, int k, float a, int ap, int64_t w, const void *b, const void *pl, const int32_t *bl, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const float *const *x, float *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8_dict_f32_i32(d, s, n, k, a, ap, w, b, pl, bl, dl, cp, cc, (const float *)cv, x, y, t); }
-    static int mul_vd(int d, void *s, int64_t n, float a, int ap, int64_t w, const void *b, const int32_t *bl, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const float *x, float *y, const vexhip_traversal *t, const vexhip_march *m)
-    { return vexhip_spmv_sell8v_march_f32_i32(d, s, n, a, ap, w, b, bl, dl, (const float *)vals, cp, cc, (const float *)cv, x, y, t, m); }
-    static int mm_vd(int d, void *s, int64_t n, int k, float a, int ap, int64_t w, const void *b, const int32_t *bl, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const float *const *x, float *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8v_dict_f32_i32(d, s, n, k, a, ap, w, b, bl, dl, (const float *)vals, cp, cc, (const float *)cv, x, y, t); }
-    static int mul_d(int d, void *s, int64_t n, float a, int ap, int64_t w, const void *b, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const float *x, float *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell8_f32_i32(d, s, n, a, ap, w, b, dl, cp, cc, (const float *)cv, x, y, t); }
-    static int mul_s(int d, void *s, int64_t n, float a, int ap, int64_t w, const void *b, const int32_t *cp, const int32_t *cc, const void *cv, const float *x, float *y, const vexhip_traversal *t)
-    { return vexhip_spmv_sell_f32_i32(d, s, n, a, ap, w, b, cp, cc, (const float *)cv, x, y, t); }
-    static int mul_c(int d, void *s, int64_t n, float a, int ap, const int32_t *p, const int32_t *c, const void *v, const float *x, float *y, const vexhip_traversal *t)
-    { return vexhip_spmv_csr_ordered_f32_i32(d, s, n, a, ap, p, c, (const float *)v, x, y, t); }
-    static int mm_v(int d, void *s, int64_t n, int k, float a, int ap, int64_t w, const void *b, const int32_t *dl, const void *vals, const int32_t *cp, const int32_t *cc, const void *cv, const float *const *x, float *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8v_f32_i32(d, s, n, k, a, ap, w, b, dl, (const float *)vals, cp, cc, (const float *)cv, x, y, t); }
-    static int mm_d(int d, void *s, int64_t n, int k, float a, int ap, int64_t w, const void *b, const int32_t *dl, const int32_t *cp, const int32_t *cc, const void *cv, const float *const *x, float *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell8_f32_i32(d, s, n, k, a, ap, w, b, dl, cp, cc, (const float *)cv, x, y, t); }
-    static int mm_s(int d, void *s, int64_t n, int k, float a, int ap, int64_t w, const void *b, const int32_t *cp, const int32_t *cc, const void *cv, const float *const *x, float *const *y, const vexhip_traversal *t)
-    { return vexhip_spmm_sell_f32_i32(d, s, n, k, a, ap, w, b, cp, cc, (const float *)cv, x, y, t); }
-};
-
 // Slice dictionary (sell8.hip): do the code blocks of the slices repeat?  Up to 128 distinct blocks (<= 1 MiB for width 7-8:
 // L1 / L2 resident) replace the code stream; anything less regular keeps it.  whole_slice: the slice is nothing but codes
-// (SELL8V) -- the per-slice storage is released; otherwise (SELL8) the values stay where they are.
-int make_dictionary(spmat *A, void *stream, int flags, int64_t code_bytes, bool whole_slice)
+// (SELL8V) -- the per-slice storage is released; otherwise (SELL8) the values stay where they are.  x_last: how far x reaches (the plans).
+template <typename V>
+int make_dictionary(spmat *A, void *stream, int flags, int64_t code_bytes, bool whole_slice, int64_t x_last)
 {
     const int64_t ns = (A->n + 511) / 512, stride = A->sell_bytes / ns;
     // (round 6: also wider than eight columns -- a constant-coefficient 27-point operator keeps 28 KiB of codes per DISTINCT slice instead of
@@ -255,7 +157,7 @@ int make_dictionary(spmat *A, void *stream, int flags, int64_t code_bytes, bool 
     void *big = nullptr; int64_t nb = -1;
     if (int rc = dmalloc(&A->blocks, (size_t)ns)) return rc;
     VEXHIP_TRY(hipMalloc(&big, (size_t)(cap * code_bytes)));
-    int rc = vexhip_slice_dictionary(A->dev, stream, ns, stride, code_bytes, A->sell, cap, A->blocks, big, &nb);
+    int rc = slice_dictionary(A->dev, stream, ns, stride, code_bytes, A->sell, cap, A->blocks, big, &nb);
     if (rc == 0 && nb > 0 && nb * 4 <= ns) {                                   // worth it only if the slices really repeat
         hipError_t e = hipMalloc(&A->pool, (size_t)(nb * code_bytes));          // the pool at its real size
         if (e == hipSuccess) e = hipMemcpyAsync(A->pool, big, (size_t)(nb * code_bytes), hipMemcpyDeviceToDevice, s);
@@ -265,17 +167,14 @@ int make_dictionary(spmat *A, void *stream, int flags, int64_t code_bytes, bool 
         A->dict_blocks = nb; A->code_bytes = code_bytes;
         if (whole_slice) { (void)hipFree(A->sell); A->sell = nullptr; A->sell_bytes = 0; }
         if (whole_slice && A->ell_w > 9 && g_sell8_variant == 0) {            // 19- / 27-point rows: decoded once per distinct slice (sell8.hip, runs of three diagonals)
-            int rc2 = A->value_type == VEXHIP_F64 ? sell8v_runs_plan(A->dev, stream, A->pool, nb, A->ell_w, A->deltas, (const double *)A->values, &A->runs)
-                                                  : sell8v_runs_plan(A->dev, stream, A->pool, nb, A->ell_w, A->deltas, (const float *)A->values, &A->runs);
-            if (rc2) return rc2;
+            if (int rc2 = sell8v_runs_plan<V>(A->dev, stream, A->pool, nb, A->ell_w, A->deltas, (const V *)A->values, &A->runs)) return rc2;
         }
         if (whole_slice && A->ell_w <= 8 && !(flags & VEXHIP_SPMAT_NO_MARCH)) {
-            const int vb = A->value_type == VEXHIP_F64 ? 8 : 4;
-            if (int rc2 = vexhip_sell8_march_plan(A->dev, stream, A->deltas, A->ndeltas, A->blocks, ns, vb,
-                                                  &A->trav, std::max<int64_t>(vexhip_sell8_last_fill_max_col(), ((flags & VEXHIP_SPMAT_SQUARE) ? A->n : 0) - 1), &A->march)) return rc2;
+            const int vb = (int)sizeof(V);
+            if (int rc2 = vexhip_sell8_march_plan(A->dev, stream, A->deltas, A->ndeltas, A->blocks, ns, vb, &A->trav, x_last, &A->march)) return rc2;
             if (!(flags & VEXHIP_SPMAT_NO_PLANE) && !env(ENV_VEXHIP_NO_PLANE512))      // (A/B: the grid product on 512-point lines)
                 if (int rc2 = vexhip_sell8_plane_plan(A->dev, stream, A->deltas, A->ndeltas, A->blocks, ns, A->pool, nb, A->ell_w, A->n, A->tail, vb,
-                                                      std::max<int64_t>(vexhip_sell8_last_fill_max_col(), ((flags & VEXHIP_SPMAT_SQUARE) ? A->n : 0) - 1), &A->plane)) return rc2;
+                                                      x_last, &A->plane)) return rc2;
         }
         return 0;
     }
@@ -283,39 +182,13 @@ int make_dictionary(spmat *A, void *stream, int flags, int64_t code_bytes, bool 
     return rc;
 }
 
-// set-up steps by row-pointer type
-template <typename V> struct setup32 {
-    typedef api<V> F;
-    static int analyze(int d, void *s, int64_t n, const int32_t *p, int64_t *w, int64_t *t) { return vexhip_hell_analyze_i32(d, s, n, p, w, t); }
-    static int tail(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const V *v, int64_t w, int32_t *cp, int32_t *cc, V *cv) { return F::hell_fill(d, s, n, p, c, v, w, (n + 15) / 16 * 16, cp, cc, cv); }
-    static int d_analyze(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, int64_t w, int32_t *dl, int *nd) { return vexhip_sell8_analyze_i32(d, s, n, p, c, w, dl, nd); }
-    static int v_analyze(int d, void *s, int64_t n, const int32_t *p, const V *v, int64_t w, V *vals, int *nv) { return F::v_analyze(d, s, n, p, v, w, vals, nv); }
-    static int v_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const V *v, int64_t w, const int32_t *dl, int nd, const V *vals, int nv, void *b, vexhip_traversal *t) { return F::v_fill(d, s, n, p, c, v, w, dl, nd, vals, nv, b, t); }
-    static int d_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const V *v, int64_t w, const int32_t *dl, int nd, void *b, vexhip_traversal *t) { return F::d_fill(d, s, n, p, c, v, w, dl, nd, b, t); }
-    static int s_fill(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const V *v, int64_t w, void *b) { return F::s_fill(d, s, n, p, c, v, w, b); }
-    static int fused(int d, void *s, int64_t n, const int32_t *p, const int32_t *c, const V *v, int64_t w, int32_t *dl, int *nd, V *vals, int *nv) { return analyze_fused_p32(d, s, n, p, c, v, w, dl, nd, vals, nv); }
-};
-template <typename V> struct setup64 {
-    static int analyze(int d, void *s, int64_t n, const long long *p, int64_t *w, int64_t *t) { return hell_analyze_p64(d, s, n, p, w, t); }
-    static int tail(int d, void *s, int64_t n, const long long *p, const int32_t *c, const V *v, int64_t w, int32_t *cp, int32_t *cc, V *cv) { return hell_tail_p64(d, s, n, p, c, v, w, cp, cc, cv); }
-    static int d_analyze(int d, void *s, int64_t n, const long long *p, const int32_t *c, int64_t w, int32_t *dl, int *nd) { return sell8_analyze_p64(d, s, n, p, c, w, dl, nd); }
-    static int v_analyze(int d, void *s, int64_t n, const long long *p, const V *v, int64_t w, V *vals, int *nv) { return sell8v_analyze_p64(d, s, n, p, v, w, vals, nv); }
-    static int v_fill(int d, void *s, int64_t n, const long long *p, const int32_t *c, const V *v, int64_t w, const int32_t *dl, int nd, const V *vals, int nv, void *b, vexhip_traversal *t) { return sell8v_fill_p64(d, s, n, p, c, v, w, dl, nd, vals, nv, b, t); }
-    static int d_fill(int d, void *s, int64_t n, const long long *p, const int32_t *c, const V *v, int64_t w, const int32_t *dl, int nd, void *b, vexhip_traversal *t) { return sell8_fill_p64(d, s, n, p, c, v, w, dl, nd, b, t); }
-    static int s_fill(int d, void *s, int64_t n, const long long *p, const int32_t *c, const V *v, int64_t w, void *b) { return sell_fill_p64(d, s, n, p, c, v, w, b); }
-    static int fused(int d, void *s, int64_t n, const long long *p, const int32_t *c, const V *v, int64_t w, int32_t *dl, int *nd, V *vals, int *nv) { return analyze_fused_p64(d, s, n, p, c, v, w, dl, nd, vals, nv); }
-};
-
 // P = int32_t or long long (row pointers); columns are 32-bit either way
 template <typename V, typename P>
 int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, const V *val, int format, int flags)
 {
-    typedef api<V> F;
-    typedef typename std::conditional<sizeof(P) == 4, setup32<V>, setup64<V>>::type S;
     constexpr bool p64 = sizeof(P) == 8;
     const int dev = A->dev;
-    A->n = n; A->value_type = F::type;
-    clear_max_col_hint();                      // a hint left by a build that failed half-way must not reach this matrix's fill
+    A->n = n; A->value_type = value_type_of<V>;
     if (n == 0) { A->format = VEXHIP_SPMAT_CSR; std::snprintf(A->why, sizeof A->why, "no rows"); return 0; }
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
@@ -339,10 +212,7 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
         if (int rc = dmalloc(&vals, 256)) return rc;
         A->values = vals;
         int nd = -1, nv = -1; int64_t gw = 0, x_last = -1;
-        int rc;
-        if constexpr (p64) rc = grid_build_p64(dev, stream, n, ptr, col, val, A->deltas, vals, &nd, &nv, &gw, &x_last, &A->grid, min_cols);
-        else rc = grid_build_p32(dev, stream, n, ptr, col, val, A->deltas, vals, &nd, &nv, &gw, &x_last, &A->grid, min_cols);
-        if (rc) return rc;
+        if (int rc = grid_build<V, P>(dev, stream, n, ptr, col, val, A->deltas, vals, &nd, &nv, &gw, &x_last, &A->grid, min_cols)) return rc;
         trace.mark("grid build");
         if (A->grid.usable) {
             A->ndeltas = nd; A->nvalues = nv; A->ell_w = gw; A->tail = 0; A->format = VEXHIP_SPMAT_SELL8V; A->direct = true;
@@ -358,7 +228,7 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
     }
     int64_t w = 0, tail = 0;
     if (format != VEXHIP_SPMAT_CSR && A->nnz > 0)
-        if (int rc = S::analyze(dev, stream, n, ptr, &w, &tail)) return rc;
+        if (int rc = hell_analyze<P>(dev, stream, n, ptr, &w, &tail)) return rc;
     trace.mark("ELL width");
     if (format == VEXHIP_SPMAT_CSR || w == 0) {
         // the CSR arrays as they are: borrowed (the caller keeps them alive) or copied
@@ -382,10 +252,7 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
             }
         }
         if constexpr (p64) A->csr_ptr64 = own_ptr; else A->csr_ptr = own_ptr;
-        if (A->nnz) {                             // strips for banded matrices
-            if constexpr (p64) (void)csr_traversal_p64(dev, stream, n, A->csr_ptr64, A->csr_col, 256, &A->trav);
-            else (void)vexhip_csr_traversal_i32(dev, stream, n, A->csr_ptr, A->csr_col, 256, &A->trav);
-        }
+        if (A->nnz) (void)csr_traversal<P>(dev, stream, n, own_ptr, A->csr_col, 256, &A->trav);      // strips for banded matrices
         VEXHIP_TRY(hipStreamSynchronize(s));
         return 0;
     }
@@ -399,20 +266,21 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
         if (int rc = dmalloc(&A->csr_col, (size_t)tail)) return rc;
         if (int rc = dmalloc(&cv, (size_t)tail)) return rc;
         A->csr_val = cv;
-        if (int rc = S::tail(dev, stream, n, ptr, col, val, w, A->csr_ptr, A->csr_col, cv)) return rc;
+        if (int rc = hell_fill<V, P>(dev, stream, n, ptr, col, val, w, (n + 15) / 16 * 16, nullptr, nullptr, A->csr_ptr, A->csr_col, cv)) return rc;
     }
     int nd = -1, nv = -1;
+    int64_t known_max_col = -1, max_col = -1;      // the largest ELL column: as the fused analysis found it (the fill then skips its own pass), as the fill stored it
     if (format == VEXHIP_SPMAT_AUTO || format == VEXHIP_SPMAT_SELL8V) {
         // both analyses are wanted: ONE pass over the CSR arrays finds the diagonals, the values and the largest ELL column
         V *vals = nullptr;
         if (int rc = dmalloc(&A->deltas, 256)) return rc;
         if (int rc = dmalloc(&vals, 256)) return rc;
         A->values = vals;
-        if (int rc = S::fused(dev, stream, n, ptr, col, val, w, A->deltas, &nd, vals, &nv)) return rc;
+        if (int rc = analyze_fused<V, P>(dev, stream, n, ptr, col, val, w, A->deltas, &nd, vals, &nv, &known_max_col)) return rc;
         trace.mark("diagonals + values");
     } else if (format != VEXHIP_SPMAT_SELL) {
         if (int rc = dmalloc(&A->deltas, 256)) return rc;
-        if (int rc = S::d_analyze(dev, stream, n, ptr, col, w, A->deltas, &nd)) return rc;
+        if (int rc = sell8_analyze<P>(dev, stream, n, ptr, col, w, A->deltas, &nd)) return rc;
     }
     if (nd > 0) {
         A->ndeltas = nd;
@@ -423,17 +291,17 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
             A->sell_bytes = vexhip_sell8v_bytes(n, w);
             VEXHIP_TRY(hipMalloc(&A->sell, (size_t)A->sell_bytes));
             trace.mark("allocate slices");
-            if (int rc = S::v_fill(dev, stream, n, ptr, col, val, w, A->deltas, nd, (const V *)A->values, nv, A->sell, &A->trav)) return rc;
-            A->ell_max_col = std::max<int64_t>(vexhip_sell8_last_fill_max_col(), min_cols - 1);
+            if (int rc = sell8v_fill<V, P>(dev, stream, n, ptr, col, val, w, A->deltas, nd, (const V *)A->values, nv, A->sell, &A->trav, known_max_col, &max_col)) return rc;
+            A->ell_max_col = std::max<int64_t>(max_col, min_cols - 1);
             trace.mark("fill");
-            if (int rc = make_dictionary(A, stream, flags, A->sell_bytes / ((n + 511) / 512), true)) return rc;
+            if (int rc = make_dictionary<V>(A, stream, flags, A->sell_bytes / ((n + 511) / 512), true, A->ell_max_col)) return rc;
             trace.mark("dictionary + plans");
             // a 7-point pattern on grid lines of another length than 512: the matrix by grid line (grid.hip), from the slices'
             // codes wherever they are now (the pool of a dictionary, or the per-slice buffer)
             if (!A->plane.usable && !tail
                 && !(flags & (VEXHIP_SPMAT_NO_DICTIONARY | VEXHIP_SPMAT_NO_MARCH | VEXHIP_SPMAT_NO_PLANE)))
                 if (int rc = vexhip_sell8_grid_plan(dev, stream, A->deltas, nd, A->blocks ? A->pool : A->sell, A->blocks, w, n, tail, (int)sizeof(V),
-                                                    std::max<int64_t>(vexhip_sell8_last_fill_max_col(), min_cols - 1), &A->grid)) return rc;
+                                                    A->ell_max_col, &A->grid)) return rc;
             trace.mark("grid plan");
         } else {
             if (A->values) { (void)hipFree(A->values); A->values = nullptr; }
@@ -442,8 +310,8 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
                           (long long)w, nd, format == VEXHIP_SPMAT_SELL8 ? " (or format SELL8 asked for)" : "", (long long)tail);
             A->sell_bytes = vexhip_sell8_bytes(n, w, (int)sizeof(V));
             VEXHIP_TRY(hipMalloc(&A->sell, (size_t)A->sell_bytes));
-            if (int rc = S::d_fill(dev, stream, n, ptr, col, val, w, A->deltas, nd, A->sell, &A->trav)) return rc;
-            if (int rc = make_dictionary(A, stream, flags, ((w + 1) / 2) * 1024, false)) return rc;
+            if (int rc = sell8_fill<V, P>(dev, stream, n, ptr, col, val, w, A->deltas, nd, A->sell, &A->trav, known_max_col, &max_col)) return rc;
+            if (int rc = make_dictionary<V>(A, stream, flags, ((w + 1) / 2) * 1024, false, std::max<int64_t>(max_col, min_cols - 1))) return rc;
         }
     } else {
         if (A->deltas) { (void)hipFree(A->deltas); A->deltas = nullptr; }
@@ -453,7 +321,7 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
                       format == VEXHIP_SPMAT_SELL ? "format SELL asked for" : "more than 254 distinct diagonals (an unstructured matrix)", (long long)tail);
         A->sell_bytes = vexhip_sell_bytes(n, w, (int)sizeof(V));
         VEXHIP_TRY(hipMalloc(&A->sell, (size_t)A->sell_bytes));
-        if (int rc = S::s_fill(dev, stream, n, ptr, col, val, w, A->sell)) return rc;
+        if (int rc = sell_fill<V, P>(dev, stream, n, ptr, col, val, w, A->sell)) return rc;
         if (int rc = vexhip_sell_order_i32(dev, stream, n, w, (int)sizeof(V), A->sell, 0, nullptr, 0, &A->trav)) return rc;
         // Round 6 -- no constant bands (an unstructured matrix): every XCD walks ONE contiguous eighth of the slices instead of every
         // eighth slice.  Where the columns of a row lie near the row (a mesh-ordered operator) the lines of x a slice gathers from are
@@ -466,7 +334,6 @@ int build(spmat *A, void *stream, int64_t n, const P *ptr, const int32_t *col, c
             A->trav.grid_blocks = 8 * per; A->trav.chunk = per; A->trav.planes = 1; A->trav.plane_blocks = ns; A->trav.order = nullptr;
         }
     }
-    clear_max_col_hint();
     VEXHIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -491,53 +358,42 @@ int create(int dev, void *stream, int64_t n, const P *ptr, const int32_t *col, c
     return 0;
 }
 
+// add: the vector the product adds in its store (vexhip_spmat_apply_axpby_*; only for the products of addend_by_store_pair)
 template <typename V>
-int apply(const spmat *A, void *stream, V alpha, int append, const V *x, V *y)
+int apply(const spmat *A, void *stream, V alpha, int append, const V *x, V *y, addend add = {})
 {
-    typedef api<V> F;
-    VEXHIP_REQUIRE(A && A->value_type == F::type, "matrix and vector value types differ");
+    VEXHIP_REQUIRE(A && A->value_type == value_type_of<V>, "matrix and vector value types differ");
     const product_choice pc = select_product(A, x, y);
+    VEXHIP_REQUIRE(!add.z || addend_by_store_pair(pc.kind), "y = alpha A x + beta z: the selected product takes no addend in its store");
     const int32_t *cp = A->tail ? A->csr_ptr : nullptr;
-    const void *tables = A->direct ? A->grid.table : A->pool;
-    const int32_t *classes = A->direct ? A->grid.line_class : A->blocks;
+    const V *values = (const V *)A->values, *cv = (const V *)A->csr_val;
     switch (pc.kind) {
         case P_NONE: return 0;
         case P_ZERO_FILL:
             if (!append) { VEXHIP_SET_DEVICE(A->dev); VEXHIP_TRY(hipMemsetAsync(y, 0, sizeof(V) * (size_t)A->n, as_stream(stream))); }
             return 0;
-        case P_PLANE64:
-            if constexpr (std::is_same<V, double>::value)
-                return vexhip_spmv_sell8v_plane_f64_i32(A->dev, stream, A->n, alpha, append, A->ell_w, tables, classes, A->deltas, (const double *)A->values, x, y, &A->plane);
-            break;
-        case P_PLANE32:
-            if constexpr (std::is_same<V, float>::value)
-                return vexhip_spmv_sell8v_plane_f32_i32(A->dev, stream, A->n, alpha, append, A->ell_w, tables, classes, A->deltas, (const float *)A->values, x, y, &A->plane);
-            break;
-        case P_GRID64:
-            if constexpr (std::is_same<V, double>::value) return vexhip_spmv_sell8v_grid_f64(A->dev, stream, A->n, alpha, append, (const double *)A->values, x, y, &A->grid);
-            break;
-        case P_GRID32:
-            if constexpr (std::is_same<V, float>::value) return vexhip_spmv_sell8v_grid_f32(A->dev, stream, A->n, alpha, append, (const float *)A->values, x, y, &A->grid);
-            break;
+        case P_PLANE64: case P_PLANE32:          // (select_product names the kind after the matrix's value type, which is V)
+            return plane_apply<V>(A->dev, stream, A->n, alpha, append, A->ell_w, tables(A), classes(A), A->deltas, values, x, y, &A->plane);
+        case P_GRID64: case P_GRID32:
+            return grid_apply<V>(A->dev, stream, A->n, alpha, append, values, x, y, &A->grid);
         case P_MARCH:
             if (A->runs && A->ell_max_col >= 0 && g_sell8_variant == 0)
-                return sell8v_runs_apply(A->dev, stream, A->n, alpha, append, A->ell_w, A->pool, A->blocks, A->deltas, (const V *)A->values, cp, A->csr_col, (const V *)A->csr_val, x, y, &A->trav, A->runs, A->ell_max_col);
-            return F::mul_vd(A->dev, stream, A->n, alpha, append, A->ell_w, A->pool, A->blocks, A->deltas, A->values, cp, A->csr_col, A->csr_val, x, y, &A->trav, &A->march);
-        case P_PAIR_CODES: return F::mul_v(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, A->deltas, A->values, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-        case P_PAIR_DICT_VALUES: return F::mul_dd(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, A->pool, A->blocks, A->deltas, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-        case P_PAIR_VALUES: return F::mul_d(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, A->deltas, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-        case P_SELL32: return F::mul_s(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-        case P_CSR64: return spmv_csr_p64(A->dev, stream, A->n, alpha, append, A->csr_ptr64, A->csr_col, (const V *)A->csr_val, x, y, &A->trav);
-        case P_CSR32: return F::mul_c(A->dev, stream, A->n, alpha, append, A->csr_ptr, A->csr_col, A->csr_val, x, y, &A->trav);
+                return sell8v_runs_apply<V>(A->dev, stream, A->n, alpha, append, A->ell_w, A->pool, A->blocks, A->deltas, values, cp, A->csr_col, cv, x, y, &A->trav, A->runs, A->ell_max_col, add);
+            return spmv_sell8v<V>(A->dev, stream, A->n, alpha, append, A->ell_w, A->pool, A->deltas, values, cp, A->csr_col, cv, x, y, &A->trav, A->blocks, A->march.usable ? &A->march : nullptr, add);
+        case P_PAIR_CODES: return spmv_sell8v<V>(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, A->deltas, values, cp, A->csr_col, cv, x, y, &A->trav, nullptr, nullptr, add);
+        case P_PAIR_DICT_VALUES: return spmv_sell8<V>(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, A->deltas, cp, A->csr_col, cv, x, y, &A->trav, A->pool, A->blocks, add);
+        case P_PAIR_VALUES: return spmv_sell8<V>(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, A->deltas, cp, A->csr_col, cv, x, y, &A->trav, nullptr, nullptr, add);
+        case P_SELL32: return spmv_sell<V>(A->dev, stream, A->n, alpha, append, A->ell_w, A->sell, cp, A->csr_col, cv, x, y, &A->trav, add);
+        case P_CSR64: return spmv_csr_wide<V>(A->dev, stream, A->n, alpha, append, A->csr_ptr64, A->csr_col, cv, x, y, &A->trav, add);
+        case P_CSR32: return spmv_csr<V, int32_t>(A->dev, stream, A->n, alpha, append, A->csr_ptr, A->csr_col, cv, x, y, &A->trav, add);
     }
-    return fail(__FILE__, __LINE__, "the selected product does not exist for this value type");
+    return fail(__FILE__, __LINE__, "unknown product");
 }
 
 template <typename V>
 int apply_multi(const spmat *A, void *stream, int k, V alpha, int append, const V *const *x, V *const *y)
 {
-    typedef api<V> F;
-    VEXHIP_REQUIRE(A && A->value_type == F::type, "matrix and vector value types differ");
+    VEXHIP_REQUIRE(A && A->value_type == value_type_of<V>, "matrix and vector value types differ");
     VEXHIP_REQUIRE(k >= 1 && x && y, "bad argument");
     if (A->n == 0) return 0;
     if (A->nnz == 0 || A->format == VEXHIP_SPMAT_CSR || A->direct) {          // no multi-vector kernel (stored by grid line: k plane / grid products beat it): one product per component
@@ -545,15 +401,44 @@ int apply_multi(const spmat *A, void *stream, int k, V alpha, int append, const 
         return 0;
     }
     const int32_t *cp = A->tail ? A->csr_ptr : nullptr;
-    switch (A->format) {
+    const V *values = (const V *)A->values, *cv = (const V *)A->csr_val;
+    switch (A->format) {           // (spmm.hip: 2 = diagonal and value codes, 1 = diagonal codes, 0 = 32-bit columns)
         case VEXHIP_SPMAT_SELL8V:
-            if (A->blocks) return F::mm_vd(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->pool, A->blocks, A->deltas, A->values, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-            return F::mm_v(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, A->deltas, A->values, cp, A->csr_col, A->csr_val, x, y, &A->trav);
+            if (A->blocks) return spmm<V, 2>(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->pool, A->deltas, values, cp, A->csr_col, cv, x, y, &A->trav, A->blocks);
+            return spmm<V, 2>(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, A->deltas, values, cp, A->csr_col, cv, x, y, &A->trav);
         case VEXHIP_SPMAT_SELL8:
-            if (A->blocks) return F::mm_dd(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, A->pool, A->blocks, A->deltas, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-            return F::mm_d(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, A->deltas, cp, A->csr_col, A->csr_val, x, y, &A->trav);
-        default:                  return F::mm_s(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, cp, A->csr_col, A->csr_val, x, y, &A->trav);
+            return spmm<V, 1>(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, A->deltas, nullptr, cp, A->csr_col, cv, x, y, &A->trav, A->blocks, A->pool);
+        default:
+            return spmm<V, 0>(A->dev, stream, A->n, k, alpha, append, A->ell_w, A->sell, nullptr, nullptr, cp, A->csr_col, cv, x, y, &A->trav);
     }
+}
+
+// y = alpha A x + beta z in ONE pass where the matrix's product can take the addend (addend_route_of), else as y = beta z followed by
+// y += alpha A x: the same two roundings and one addition per element either way.
+template <typename V>
+int apply_axpby(const spmat *A, void *stream, V alpha, const V *x, V beta, const V *z, V *y)
+{
+    VEXHIP_REQUIRE(A && A->value_type == value_type_of<V>, "matrix and vector value types differ");
+    VEXHIP_REQUIRE(x && y && z, "NULL argument");
+    VEXHIP_REQUIRE(static_cast<const void *>(x) != static_cast<const void *>(y), "y = alpha A x + beta z: x and y are the same vector");
+    if (A->n == 0) return 0;
+    const product_kind kind = select_product(A, x, y).kind;
+    switch (addend_route_of(kind, x, z)) {
+        case ADD_WALK:
+            if (kind == P_PLANE64 || kind == P_PLANE32)
+                return plane_apply_axpby(A->dev, stream, A->n, alpha, z == x ? 2 : 1, z, beta, A->ell_w, tables(A), classes(A), A->deltas, (const V *)A->values, x, y, &A->plane);
+            return grid_apply_axpby(A->dev, stream, A->n, alpha, z == x ? 2 : 1, z, beta, (const V *)A->values, x, y, &A->grid);
+        case ADD_STORE: return apply<V>(A, stream, alpha, 0, x, y, addend{z, (double)beta});
+        case ADD_NONE: break;
+    }
+    if (!(z == y && beta == V(1))) {
+        VEXHIP_SET_DEVICE(A->dev);
+        const long long grid = (A->n + 255) / 256;
+        VEXHIP_REQUIRE(grid < (1ll << 31), "vector too large for one launch");
+        scale_into_kernel<V><<<(unsigned)grid, 256, 0, as_stream(stream)>>>(y, z, beta, (long long)A->n);
+        VEXHIP_LAUNCH_CHECK();
+    }
+    return apply<V>(A, stream, alpha, 1, x, y);
 }
 
 } // namespace
@@ -605,38 +490,16 @@ int spmat_apply_halo(const vexhip_spmat *h, hipStream_t s, double alpha, int app
     VEXHIP_REQUIRE(A && A->format == VEXHIP_SPMAT_SELL8V && !A->tail, "the one-launch step needs a matrix stored for the plane or the grid product");
     if (A->value_type == VEXHIP_F32) {
         VEXHIP_REQUIRE((A->blocks || A->direct) && A->plane.usable && H.pull, "the one-launch step of a float matrix needs the plane product and shares read in place");
-        return plane32_apply_halo(A->dev, s, A->n, (float)alpha, append, A->ell_w, A->direct ? A->grid.table : A->pool,
-                                  A->direct ? A->grid.line_class : A->blocks, A->deltas, (const float *)A->values, static_cast<const float *>(x), static_cast<float *>(y), &A->plane, H);
+        return plane_apply_halo(A->dev, s, A->n, (float)alpha, append, A->ell_w, tables(A), classes(A), A->deltas, (const float *)A->values, static_cast<const float *>(x), static_cast<float *>(y), &A->plane, H);
     }
     if ((A->blocks || A->direct) && A->plane.usable)
-        return plane_apply_halo(A->dev, s, A->n, alpha, append, A->ell_w, A->direct ? A->grid.table : A->pool,
-                                A->direct ? A->grid.line_class : A->blocks, A->deltas, (const double *)A->values, static_cast<const double *>(x), static_cast<double *>(y), &A->plane, H);
+        return plane_apply_halo(A->dev, s, A->n, alpha, append, A->ell_w, tables(A), classes(A), A->deltas, (const double *)A->values, static_cast<const double *>(x), static_cast<double *>(y), &A->plane, H);
     VEXHIP_REQUIRE(A->grid.usable && H.pull, "the one-launch step needs a matrix stored for the plane product (pushed shares) or the grid product (shares read in place)");
     return grid_apply_halo(A->dev, s, A->n, alpha, append, (const double *)A->values, static_cast<const double *>(x), static_cast<double *>(y), &A->grid, H);
 }
 } // namespace vexhip
 
 using namespace vexhip;
-
-namespace {
-// products whose launcher hands the addend to its kernels' store_pair (traversal.hpp): the pair / any-width products of the coded storages
-// and of the 32-bit columns, the CSR kernels and the march product in their own epilogues
-inline bool addend_by_store_pair(const spmat *A, product_kind k) {
-    return k == P_PAIR_CODES || k == P_PAIR_DICT_VALUES || k == P_PAIR_VALUES || k == P_SELL32 || k == P_MARCH || k == P_CSR32 || k == P_CSR64;
-}
-template <typename V>
-int apply_with_addend(const spmat *A, void *stream, V alpha, const V *x, V beta, const V *z, V *y) {
-    pending_addend &a = next_addend();
-    a.z = z; a.beta = (double)beta; a.taken = false;
-    const int rc = apply<V>(A, stream, alpha, 0, x, y);
-    const bool taken = a.taken;
-    a = pending_addend();
-    if (rc) return rc;
-    if (!taken) return fail(__FILE__, __LINE__, "y = alpha A x + beta z: the product that ran took no addend (select_product and the launchers disagree)");
-    return 0;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -663,65 +526,17 @@ int vexhip_spmat_apply_f64(const vexhip_spmat *A, void *stream, double alpha, in
 int vexhip_spmat_apply_f32(const vexhip_spmat *A, void *stream, float alpha, int append, const float *x, float *y)
 { return apply<float>(reinterpret_cast<const spmat *>(A), stream, alpha, append, x, y); }
 
-// y = alpha A x + beta z in ONE pass where the matrix's product can take the addend (the plane product: from z, or -- z == x -- from the
-// registers that hold x anyway), else as y = beta z followed by y += alpha A x: the same two roundings and one addition per element either way.
-int vexhip_spmat_apply_axpby_f64(const vexhip_spmat *h, void *stream, double alpha, const double *x, double beta, const double *z, double *y)
-{
-    const spmat *A = reinterpret_cast<const spmat *>(h);
-    VEXHIP_REQUIRE(A && A->value_type == VEXHIP_F64, "matrix and vector value types differ");
-    VEXHIP_REQUIRE(x && y && z, "NULL argument");
-    VEXHIP_REQUIRE(static_cast<const void *>(x) != static_cast<const void *>(y), "y = alpha A x + beta z: x and y are the same vector");
-    if (A->n == 0) return 0;
-    const product_choice pc = select_product(A, x, y);
-    if (pc.kind == P_PLANE64 && (z == x || (reinterpret_cast<uintptr_t>(z) & 15) == 0))
-        return plane_apply_axpby(A->dev, stream, A->n, alpha, z == x ? 2 : 1, z, beta, A->ell_w, A->direct ? A->grid.table : A->pool,
-                                 A->direct ? A->grid.line_class : A->blocks, A->deltas, (const double *)A->values, x, y, &A->plane);
-    if (pc.kind == P_GRID64 && (reinterpret_cast<uintptr_t>(z) & 7) == 0)
-        return grid_apply_axpby(A->dev, stream, A->n, alpha, z == x ? 2 : 1, z, beta, (const double *)A->values, x, y, &A->grid);
-    if (addend_by_store_pair(A, pc.kind)) return apply_with_addend<double>(A, stream, alpha, x, beta, z, y);
-    if (!(z == y && beta == 1.0)) {
-        VEXHIP_SET_DEVICE(A->dev);
-        const long long grid = (A->n + 255) / 256;
-        VEXHIP_REQUIRE(grid < (1ll << 31), "vector too large for one launch");
-        scale_into_kernel<double><<<(unsigned)grid, 256, 0, as_stream(stream)>>>(y, z, beta, (long long)A->n);
-        VEXHIP_LAUNCH_CHECK();
-    }
-    return apply<double>(A, stream, alpha, 1, x, y);
-}
-
-int vexhip_spmat_apply_axpby_f32(const vexhip_spmat *h, void *stream, float alpha, const float *x, float beta, const float *z, float *y)
-{
-    const spmat *A = reinterpret_cast<const spmat *>(h);
-    VEXHIP_REQUIRE(A && A->value_type == VEXHIP_F32, "matrix and vector value types differ");
-    VEXHIP_REQUIRE(x && y && z, "NULL argument");
-    VEXHIP_REQUIRE(static_cast<const void *>(x) != static_cast<const void *>(y), "y = alpha A x + beta z: x and y are the same vector");
-    if (A->n == 0) return 0;
-    const product_choice pc = select_product(A, x, y);
-    if (pc.kind == P_PLANE32)
-        return plane32_apply_axpby(A->dev, stream, A->n, alpha, z == x ? 2 : 1, z, beta, A->ell_w, A->direct ? A->grid.table : A->pool,
-                                   A->direct ? A->grid.line_class : A->blocks, A->deltas, (const float *)A->values, x, y, &A->plane);
-    if (pc.kind == P_GRID32)
-        return grid32_apply_axpby(A->dev, stream, A->n, alpha, z == x ? 2 : 1, z, beta, (const float *)A->values, x, y, &A->grid);
-    if (addend_by_store_pair(A, pc.kind)) return apply_with_addend<float>(A, stream, alpha, x, beta, z, y);
-    if (!(z == y && beta == 1.0f)) {
-        VEXHIP_SET_DEVICE(A->dev);
-        const long long grid = (A->n + 255) / 256;
-        VEXHIP_REQUIRE(grid < (1ll << 31), "vector too large for one launch");
-        scale_into_kernel<float><<<(unsigned)grid, 256, 0, as_stream(stream)>>>(y, z, beta, (long long)A->n);
-        VEXHIP_LAUNCH_CHECK();
-    }
-    return apply<float>(A, stream, alpha, 1, x, y);
-}
+int vexhip_spmat_apply_axpby_f64(const vexhip_spmat *A, void *stream, double alpha, const double *x, double beta, const double *z, double *y)
+{ return apply_axpby<double>(reinterpret_cast<const spmat *>(A), stream, alpha, x, beta, z, y); }
+int vexhip_spmat_apply_axpby_f32(const vexhip_spmat *A, void *stream, float alpha, const float *x, float beta, const float *z, float *y)
+{ return apply_axpby<float>(reinterpret_cast<const spmat *>(A), stream, alpha, x, beta, z, y); }
 
 // 1: vexhip_spmat_apply_axpby_f64 on these vectors runs as ONE pass (the product takes the addend); 0: as y = beta z, y += alpha A x
 int vexhip_spmat_axpby_fused(const vexhip_spmat *h, const void *x, const void *z, const void *y)
 {
     const spmat *A = reinterpret_cast<const spmat *>(h);
     if (!A || !x || !y || !z || x == y || A->n == 0) return 0;
-    const product_kind k = select_product(A, x, y).kind;
-    if (addend_by_store_pair(A, k)) return 1;
-    if (A->value_type == VEXHIP_F32) return k == P_PLANE32 || k == P_GRID32 ? 1 : 0;
-    return (k == P_PLANE64 && (z == x || (reinterpret_cast<uintptr_t>(z) & 15) == 0)) || (k == P_GRID64 && (reinterpret_cast<uintptr_t>(z) & 7) == 0) ? 1 : 0;
+    return addend_route_of(select_product(A, x, y).kind, x, z) != ADD_NONE ? 1 : 0;
 }
 
 int vexhip_spmat_apply_multi_f64(const vexhip_spmat *A, void *stream, int nrhs, double alpha, int append, const double *const *x, double *const *y)

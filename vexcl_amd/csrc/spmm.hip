@@ -12,6 +12,7 @@
 // -ffp-contract=off too), so every Y_k is bit-identical to the separate product.
 #include "common.hpp"
 #include "traversal.hpp"
+#include "storage.hpp"
 
 namespace vexhip {
 namespace {
@@ -308,9 +309,12 @@ void launch(hipStream_t s, long long grid, long long n, long long ns, V alpha, i
 #undef LAUNCH
 }
 
+} // namespace
+
+// nrhs products in passes of up to MAX_NR right-hand sides (storage.hpp)
 template <typename V, int CODES>
 int spmm(int dev, void *stream, int64_t n, int nrhs, V alpha, int append, int64_t w, const void *buf, const int *deltas, const V *values,
-        const int *cp, const int *cc, const V *cv, const V *const *x, V *const *y, const vexhip_traversal *tr, const int *blocks = nullptr, const void *pool_ = nullptr)
+        const int *cp, const int *cc, const V *cv, const V *const *x, V *const *y, const vexhip_traversal *tr, const int *blocks, const void *pool_)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 1 && w < (1 << 20) && nrhs >= 1, "bad SpMM geometry");
     if (n == 0) return 0;
@@ -339,7 +343,11 @@ int spmm(int dev, void *stream, int64_t n, int nrhs, V alpha, int append, int64_
     return 0;
 }
 
-} // namespace
+#define VEXHIP_INSTANTIATE(V, CODES) template int spmm<V, CODES>(int, void *, int64_t, int, V, int, int64_t, const void *, const int *, const V *, const int *, const int *, const V *, \
+        const V *const *, V *const *, const vexhip_traversal *, const int *, const void *);
+VEXHIP_INSTANTIATE(double, 0) VEXHIP_INSTANTIATE(double, 1) VEXHIP_INSTANTIATE(double, 2) VEXHIP_INSTANTIATE(float, 0) VEXHIP_INSTANTIATE(float, 1) VEXHIP_INSTANTIATE(float, 2)
+#undef VEXHIP_INSTANTIATE
+
 } // namespace vexhip
 
 using namespace vexhip;

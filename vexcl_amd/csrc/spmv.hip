@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "traversal.hpp"
 #include "pairing.hpp"
+#include "storage.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -22,7 +23,6 @@
 #include <vector>
 
 namespace vexhip {
-extern int g_sell8_variant;                                   // sell8.hip: 0 = pair kernels (default), 1 = one gather per entry
 namespace {
 
 typedef int    int2v  __attribute__((ext_vector_type(2)));
@@ -568,43 +568,6 @@ constexpr int kHellDefault = 7;   // RPT = 2, nontemporal streams, XCD-contiguou
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <typename V, typename I>
-int spmv_csr(int dev, void *stream, int64_t n, V alpha, int append,
-        const I *ptr, const I *col, const V *val, const V *x, V *y, const vexhip_traversal *tr = nullptr)
-{
-    VEXHIP_REQUIRE(n >= 0, "negative row count");
-    if (n == 0) return 0;
-    VEXHIP_REQUIRE(ptr && x && y, "NULL argument");
-    VEXHIP_SET_DEVICE(dev);
-    hipStream_t s = as_stream(stream);
-    if (!aligned16(col) || !aligned16(val)) {
-        int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)info(dev).cus * 32);
-        const trav_dev ad = with_addend(trav_dev{nullptr, 0, 0, 0});
-        csr_scalar_kernel<V, I><<<grid, 256, 0, s>>>(n, alpha, append, ptr, col, val, x, y, static_cast<const V *>(ad.z), (V)ad.beta);
-        VEXHIP_LAUNCH_CHECK();
-        return 0;
-    }
-    long long nb = (n + CSR_BLOCK - 1) / CSR_BLOCK;
-    int variant = g_csr_variant < 0 ? kCsrDefault : g_csr_variant;
-    bool nt = variant & 1, swz = variant & 2;
-    long long grid = swz ? ((nb + 7) / 8) * 8 : nb;
-    trav_dev order = {nullptr, 0, 0, 0};
-    if (tr && tr->grid_blocks > 0) order = make_traversal(tr, nb, &grid);
-    order = with_addend(order);                                    // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*)
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-#define LAUNCH(NT, SWZ) csr_stream_kernel<V, I, NT, SWZ><<<(unsigned)grid, CSR_BLOCK, 0, s>>>( \
-        n, nb, alpha, append, ptr, col, val, x, y, order)
-    if (!(variant & 4)) {             // second form (default)
-        if (swz) csr_stream2_kernel<V, I, true, 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
-        else csr_stream2_kernel<V, I, false, 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
-    }
-    else if (nt) { if (swz) LAUNCH(true, true); else LAUNCH(true, false); }
-    else    { if (swz) LAUNCH(false, true); else LAUNCH(false, false); }
-#undef LAUNCH
-    VEXHIP_LAUNCH_CHECK();
-    return 0;
-}
-
 template <typename V>
 int spmv_csr_rows(int dev, void *stream, int64_t nr, V alpha, const int *rows, const int *ptr, const int *col,
         const V *val, const V *x, V *y)
@@ -692,10 +655,34 @@ int spmv_hell(int dev, void *stream, int64_t n, V alpha, int append,
     return 0;
 }
 
+// Agreement of every ELL column j with a constant offset col - row == ref[j].
+__global__ __launch_bounds__(256)
+void ell_offset_agree_kernel(long long n, int w, long long pitch, const int *__restrict__ ell_col,
+        const long long *__restrict__ ref, unsigned long long *__restrict__ agree)
+{
+    for (int j = 0; j < w; ++j) {
+        unsigned long long local = 0;
+        const long long off = ref[j];
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+             i += (long long)gridDim.x * blockDim.x) {
+            // pitch < 0: SELL-512 storage with (-pitch)-byte values; index in ints from the buffer start
+            long long e = pitch > 0 ? i + j * pitch
+                                    : (i / SELL_ROWS) * ((long long)w * SELL_ROWS * (4 - pitch) / 4) + (long long)j * SELL_ROWS + i % SELL_ROWS;
+            int c = ell_col[e];
+            local += (c >= 0 && (long long)c - i == off) ? 1ull : 0ull;
+        }
+        for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
+        if ((threadIdx.x & 63) == 0 && local) atomicAdd(&agree[j], local);
+    }
+}
+
+} // namespace
+
+// ---- the typed products and the SELL fill (storage.hpp) ----
 template <typename V>
 int spmv_sell(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
         const void *sell, const int *cp, const int *cc, const V *cv, const V *x, V *y,
-        const vexhip_traversal *tr)
+        const vexhip_traversal *tr, addend add)
 {
     VEXHIP_REQUIRE(n >= 0 && w >= 1 && w < (1 << 20), "bad SELL geometry");
     if (n == 0) return 0;
@@ -708,7 +695,7 @@ int spmv_sell(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
     long long grid = ordered ? tr->grid_blocks : ns;
     trav_dev order = {nullptr, 0, 0, 0};
     if (ordered) order = trav_dev{tr->order, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
-    order = with_addend(order);                                    // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
+    order = attach(order, add);                                    // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
 #define CASE(W) case W: if (g_sell8_variant == 0) sell_pair_kernel<V, W><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, sc, cp, cc, cv, x, y, order); \
         else sell_kernel<V, W, true><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, sc, cp, cc, cv, x, y, order); break;
@@ -744,42 +731,49 @@ int sell_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, co
     return check(e, __FILE__, __LINE__);
 }
 
-// Agreement of every ELL column j with a constant offset col - row == ref[j].
-__global__ __launch_bounds__(256)
-void ell_offset_agree_kernel(long long n, int w, long long pitch, const int *__restrict__ ell_col,
-        const long long *__restrict__ ref, unsigned long long *__restrict__ agree)
+template <typename V, typename I>
+int spmv_csr(int dev, void *stream, int64_t n, V alpha, int append,
+        const I *ptr, const I *col, const V *val, const V *x, V *y, const vexhip_traversal *tr, addend add)
 {
-    for (int j = 0; j < w; ++j) {
-        unsigned long long local = 0;
-        const long long off = ref[j];
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-             i += (long long)gridDim.x * blockDim.x) {
-            // pitch < 0: SELL-512 storage with (-pitch)-byte values; index in ints from the buffer start
-            long long e = pitch > 0 ? i + j * pitch
-                                    : (i / SELL_ROWS) * ((long long)w * SELL_ROWS * (4 - pitch) / 4) + (long long)j * SELL_ROWS + i % SELL_ROWS;
-            int c = ell_col[e];
-            local += (c >= 0 && (long long)c - i == off) ? 1ull : 0ull;
-        }
-        for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-        if ((threadIdx.x & 63) == 0 && local) atomicAdd(&agree[j], local);
+    VEXHIP_REQUIRE(n >= 0, "negative row count");
+    if (n == 0) return 0;
+    VEXHIP_REQUIRE(ptr && x && y, "NULL argument");
+    VEXHIP_SET_DEVICE(dev);
+    hipStream_t s = as_stream(stream);
+    if (!aligned16(col) || !aligned16(val)) {
+        int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)info(dev).cus * 32);
+        csr_scalar_kernel<V, I><<<grid, 256, 0, s>>>(n, alpha, append, ptr, col, val, x, y, static_cast<const V *>(add.z), (V)add.beta);
+        VEXHIP_LAUNCH_CHECK();
+        return 0;
     }
+    long long nb = (n + CSR_BLOCK - 1) / CSR_BLOCK;
+    int variant = g_csr_variant < 0 ? kCsrDefault : g_csr_variant;
+    bool nt = variant & 1, swz = variant & 2;
+    long long grid = swz ? ((nb + 7) / 8) * 8 : nb;
+    trav_dev order = {nullptr, 0, 0, 0};
+    if (tr && tr->grid_blocks > 0) order = make_traversal(tr, nb, &grid);
+    order = attach(order, add);                                    // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*)
+    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
+#define LAUNCH(NT, SWZ) csr_stream_kernel<V, I, NT, SWZ><<<(unsigned)grid, CSR_BLOCK, 0, s>>>( \
+        n, nb, alpha, append, ptr, col, val, x, y, order)
+    if (!(variant & 4)) {             // second form (default)
+        if (swz) csr_stream2_kernel<V, I, true, 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
+        else csr_stream2_kernel<V, I, false, 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
+    }
+    else if (nt) { if (swz) LAUNCH(true, true); else LAUNCH(true, false); }
+    else    { if (swz) LAUNCH(false, true); else LAUNCH(false, false); }
+#undef LAUNCH
+    VEXHIP_LAUNCH_CHECK();
+    return 0;
 }
-
-} // namespace
-
-// ---- 64-bit row pointers with 32-bit columns (round 3): internal entry points for spmat.hip ---------------------------
-int sell_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const double *val, int64_t w, void *sell)
-{ return sell_fill<double, long long>(dev, stream, n, ptr, col, val, w, sell); }
-int sell_fill_p64(int dev, void *stream, int64_t n, const long long *ptr, const int32_t *col, const float *val, int64_t w, void *sell)
-{ return sell_fill<float, long long>(dev, stream, n, ptr, col, val, w, sell); }
 
 // The CSR arrays themselves with 64-bit row pointers (2^31 entries or more kept in CSR): the staged kernel with 64-bit row
 // bounds, strips as for 32-bit pointers (spmat.hip passes the traversal).  Round 3 ran the reference's one-row-per-work-item
 // loop here (spmat/csr.inl:153-171; 30 ms at 700^3) because this instantiation took 120 s and faulted: lanes without a row in
 // the ragged last workgroup -- see the fold of csr_stream2_kernel.  Arrays that are not 16-byte aligned keep the plain loop.
 template <typename V>
-int spmv_csr_p64_impl(int dev, void *stream, int64_t n, V alpha, int append, const long long *ptr, const int32_t *col, const V *val, const V *x, V *y,
-        const vexhip_traversal *tr) {
+int spmv_csr_wide(int dev, void *stream, int64_t n, V alpha, int append, const long long *ptr, const int32_t *col, const V *val, const V *x, V *y,
+        const vexhip_traversal *tr, addend add) {
     VEXHIP_REQUIRE(n >= 0, "negative row count");
     if (n == 0) return 0;
     VEXHIP_REQUIRE(ptr && x && y, "NULL argument");
@@ -787,8 +781,7 @@ int spmv_csr_p64_impl(int dev, void *stream, int64_t n, V alpha, int append, con
     hipStream_t s = as_stream(stream);
     if (!aligned16(col) || !aligned16(val) || g_csr_variant == 8) {
         const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)info(dev).cus * 32);
-        const trav_dev ad = with_addend(trav_dev{nullptr, 0, 0, 0});
-        csr_scalar_kernel<V, int, long long><<<grid, 256, 0, s>>>(n, alpha, append, ptr, col, val, x, y, static_cast<const V *>(ad.z), (V)ad.beta);
+        csr_scalar_kernel<V, int, long long><<<grid, 256, 0, s>>>(n, alpha, append, ptr, col, val, x, y, static_cast<const V *>(add.z), (V)add.beta);
         VEXHIP_LAUNCH_CHECK();
         return 0;
     }
@@ -797,17 +790,22 @@ int spmv_csr_p64_impl(int dev, void *stream, int64_t n, V alpha, int append, con
     trav_dev order = {nullptr, 0, 0, 0};
     const bool strips = tr && tr->grid_blocks > 0;
     if (strips) order = make_traversal(tr, nb, &grid);
-    order = with_addend(order);
+    order = attach(order, add);
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     if (strips) csr_stream2_kernel<V, int, false, 2048, long long><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
     else csr_stream2_kernel<V, int, true, 2048, long long><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
-int spmv_csr_p64(int dev, void *stream, int64_t n, double alpha, int append, const long long *ptr, const int32_t *col, const double *val, const double *x, double *y, const vexhip_traversal *tr)
-{ return spmv_csr_p64_impl<double>(dev, stream, n, alpha, append, ptr, col, val, x, y, tr); }
-int spmv_csr_p64(int dev, void *stream, int64_t n, float alpha, int append, const long long *ptr, const int32_t *col, const float *val, const float *x, float *y, const vexhip_traversal *tr)
-{ return spmv_csr_p64_impl<float>(dev, stream, n, alpha, append, ptr, col, val, x, y, tr); }
+
+#define VEXHIP_INSTANTIATE(V) \
+    template int sell_fill<V, int32_t>(int, void *, int64_t, const int32_t *, const int *, const V *, int64_t, void *); \
+    template int sell_fill<V, long long>(int, void *, int64_t, const long long *, const int *, const V *, int64_t, void *); \
+    template int spmv_sell<V>(int, void *, int64_t, V, int, int64_t, const void *, const int *, const int *, const V *, const V *, V *, const vexhip_traversal *, addend); \
+    template int spmv_csr<V, int>(int, void *, int64_t, V, int, const int *, const int *, const V *, const V *, V *, const vexhip_traversal *, addend); \
+    template int spmv_csr_wide<V>(int, void *, int64_t, V, int, const long long *, const int32_t *, const V *, const V *, V *, const vexhip_traversal *, addend);
+VEXHIP_INSTANTIATE(double) VEXHIP_INSTANTIATE(float)
+#undef VEXHIP_INSTANTIATE
 
 } // namespace vexhip
 

@@ -11,15 +11,9 @@ namespace vexhip {
 // the traversal because every SELL-family kernel takes one by value and ends in store_pair
 struct trav_dev { const int *order; int chunk, planes, plane_blocks; const void *z = nullptr; double beta = 0.0; };
 
-// The addend of the NEXT product launched on this thread (set by vexhip_spmat_apply_axpby_*, taken -- and thereby marked as taken -- by
-// the launchers that pass it on; a launcher that does not know it leaves it, and the caller reports an error instead of a wrong y).
-struct pending_addend { const void *z = nullptr; double beta = 0.0; bool taken = false; };
-inline pending_addend &next_addend() { static thread_local pending_addend a; return a; }
-inline trav_dev with_addend(trav_dev t) {
-    pending_addend &a = next_addend();
-    if (a.z) { t.z = a.z; t.beta = a.beta; a.taken = true; }
-    return t;
-}
+// What a launcher is handed when its product is to add a vector (a trailing argument of the typed products, storage.hpp; default: none)
+struct addend { const void *z = nullptr; double beta = 0.0; };
+inline trav_dev attach(trav_dev t, const addend &a) { t.z = a.z; t.beta = a.beta; return t; }
 
 /// Slice of virtual block `vb` (the kernels that loop over several slices pass vb = blockIdx.x + k * gridDim.x;
 /// a grid that is a multiple of 8 keeps every block on the XCD strip it started on).  Launch grids are
@@ -76,7 +70,7 @@ inline trav_dev make_traversal(const vexhip_traversal *tr, long long nblocks, lo
         t = trav_dev{tr->order, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
         *grid = tr->grid_blocks;
     }
-    return t;                          // (the addend is attached by the launchers that pass it on: with_addend)
+    return t;                          // (the addend is attached by the launchers that pass it on: attach)
 }
 
 } // namespace vexhip
