@@ -11,6 +11,13 @@
 //   rows    the rows that have remote entries, compacted (row-subset CSR: 2 planes of 64 for 512^3 over 8 GPUs)
 //   ghosts  sort (sort.hip) + unique of the remote columns -> the sorted ghost set; then every remote column is
 //           replaced by its rank in that set (binary search)
+//
+// Contract of the outputs at the edges (include/vexhip.h lists the arrays, INTEGRATION.md section 4 repeats this beside the
+// calling sequence, tests/test_gpu_partition_kernels.py holds it): both
+// row-pointer arrays are complete CSR row pointers in every case -- a strip without rows (n == 0) gets lptr[0] = 0, a strip
+// without remote entries gets rem_ptr[0] = 0 (a row-subset CSR of zero rows); sizes() leaves sizes[3] = -1 for every n; arrays
+// of zero elements may be NULL and are not touched; col_begin == col_end is allowed (every entry is remote), col_end < col_begin
+// is refused.
 #include "common.hpp"
 
 #include <vector>
@@ -130,7 +137,14 @@ int split(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *c
     VEXHIP_REQUIRE(sizes, "NULL sizes");
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    if (n == 0) { sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0; return 0; }
+    if (n == 0) {
+        // a strip without rows: both parts are CSR matrices of zero rows, ptr == [0] (sizes() has phase 0 and no arrays)
+        sizes[0] = sizes[1] = sizes[2] = 0; sizes[3] = phase ? 0 : -1;
+        if (lptr) VEXHIP_TRY(hipMemsetAsync(lptr, 0, sizeof(int), s));
+        if (rem_ptr) VEXHIP_TRY(hipMemsetAsync(rem_ptr, 0, sizeof(int), s));
+        if (phase) VEXHIP_TRY(hipStreamSynchronize(s));       // split() returns with its outputs written, as for n > 0
+        return 0;
+    }
     VEXHIP_REQUIRE(ptr, "NULL row pointers");          // col / val may be NULL for a strip without entries
     scratch S;
     int *lcnt, *rcnt, *lp, *rp;
@@ -194,6 +208,8 @@ int split(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *c
         sizes[3] = ng;
         rank_kernel<<<grid_for(dev, rnnz), 256, 0, s>>>(rnnz, rem_col, ghosts, ng);
         VEXHIP_LAUNCH_CHECK();
+    } else if (rem_ptr) {
+        VEXHIP_TRY(hipMemsetAsync(rem_ptr, 0, sizeof(int), s));    // no remote entry: a row-subset CSR of zero rows, ptr == [0]
     }
     VEXHIP_TRY(hipStreamSynchronize(s));
     return 0;
