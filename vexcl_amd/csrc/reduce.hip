@@ -244,6 +244,7 @@ int vexhip_reduce(int dev, void *stream, int op, int dtype, const void *in, int6
 
 int vexhip_reduce_dot(int dev, void *stream, int dtype, const void *a, const void *b, int64_t n, void *out, void *tmp) {
     VEXHIP_REQUIRE(out && tmp && n >= 0, "bad argument");
+    VEXHIP_REQUIRE(info(dev).cus * 8 * 16 <= (int64_t)vexhip_reduce_tmp_bytes(), "tmp too small for this device");
     VEXHIP_SET_DEVICE(dev);
     DISPATCH(dot_t, dev, stream, a, b, n, out, tmp)
 }

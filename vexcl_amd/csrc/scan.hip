@@ -324,7 +324,9 @@ int scan_lookback(hipStream_t s, const T *in, T *out, int64_t n, bool exclusive,
     int64_t nt = (n + tile - 1) / tile;
     VEXHIP_REQUIRE(nt < (1ll << 31), "scan too large");
     unsigned long long *ws = reinterpret_cast<unsigned long long *>(tmp);
-    VEXHIP_TRY(hipMemsetAsync(ws, 0, (2 + (size_t)nt * 2) * 8, s));
+    // the ticket word, the reserved word and the status words of THIS form's tiles: nt is at most the tile count that
+    // lookback_words() sizes for, so the cleared range lies inside vexhip_scan_tmp_bytes without its slack
+    VEXHIP_TRY(hipMemsetAsync(ws, 0, (2 + (size_t)nt * tile_status<T>::WORDS) * 8, s));
 #define GO(LSK, BLK) do { \
         if (exclusive) lookback_scan_kernel<T, true, LSK, BLK><<<(unsigned)nt, BLK, 0, s>>>(in, out, n, init, ws, vec_ok); \
         else           lookback_scan_kernel<T, false, LSK, BLK><<<(unsigned)nt, BLK, 0, s>>>(in, out, n, init, ws, vec_ok); } while (0)
