@@ -816,6 +816,82 @@ def _axpby_placements(T, oracle, A, ptr, col, val, what):
         assert np.array_equal(dy.cpu().numpy(), vt(beta) * y0 + ax), (what, alpha, beta, "z = y")
 
 
+# (value type, grid, VEXHIP_PLANE_TILE, the product expected): the smallest shapes that reach each launch form of the four structured products
+_STORE_CASES = {
+    "f64-plane-tile2": (np.float64, (512, 6, 8), None, "sell8_plane_kernel"),
+    "f64-plane-tile4": (np.float64, (512, 8, 6), 4, "sell8_plane_kernel"),
+    "f64-plane-flat": (np.float64, (3072, 40, 1), None, "sell8_plane_kernel"),      # a 5-point operator on six virtual 512-point lines per row
+    "f64-grid-256": (np.float64, (70, 11, 13), None, "sell8_grid_kernel"),
+    "f64-grid-512": (np.float64, (1030, 5, 9), None, "sell8_grid_kernel"),          # workgroups of more than 256 lanes
+    "f32-plane": (np.float32, (512, 6, 8), None, "sell8_plane_f32_kernel"),
+    "f32-grid-256": (np.float32, (70, 11, 13), None, "sell8_grid_f32_kernel"),
+    "f32-grid-1030": (np.float32, (1030, 5, 9), None, "sell8_grid_f32_kernel"),
+}
+_STORE_ALPHA_BETA = ((-1.0, 1.0), (0.5, -0.25))
+_store_case_cache = {}
+
+
+def _store_case(oracle, name):
+    """the matrix, the vectors and alpha A x on the host of one case of _STORE_CASES: computed once, shared by the five store policies"""
+    if name not in _store_case_cache:
+        vt, shape = _STORE_CASES[name][:2]
+        ptr, col, val = _grid7_natural(*shape)
+        val = val.astype(vt)
+        m = len(ptr) - 1
+        x, z, y0 = (oracle.random_f64(seed, m).astype(vt) for seed in (11, 12, 13))
+        ax = {alpha: oracle.spmv_csr(ptr, col, val, x, alpha=alpha) for alpha, _ in _STORE_ALPHA_BETA}
+        _store_case_cache[name] = (ptr, col, val, x, z, y0, ax)
+    return _store_case_cache[name]
+
+
+@pytest.mark.parametrize("store", [None, 0, 1, 2, 3])
+@pytest.mark.parametrize("name", sorted(_STORE_CASES))
+def test_structured_products_every_store_policy_and_addend(T, oracle, built_lib, name, store):
+    """The launches of the plane and grid products choose a kernel instantiation by the addend of the result (none, an array, x itself) and
+    by the cache policy of the y stores (VEXHIP_PLANE_STORE 0 .. 3; unset: 1, 2 for the fp64 plane product on tiles of four lines): every
+    pair, on every launch form -- fp64 plane product on tiles of two and four lines and on a flat plan, fp64 grid product with up to and
+    more than 256 lanes, fp32 plane and grid products -- bit for bit against the host evaluation of
+    test_product_with_a_vector_added_is_bit_identical.  The policy is part of the plan (the fp32 plane product alone reads the switch
+    when it launches: only its results can be checked)."""
+    saved = {k: os.environ.get(k) for k in ("VEXHIP_PLANE_STORE", "VEXHIP_PLANE_TILE", "VEXHIP_PLANE_FORCE")}
+    try:
+        vt, shape, tile, product = _STORE_CASES[name]
+        ptr, col, val, x, z, y0, ax = _store_case(oracle, name)
+        m = len(ptr) - 1
+        os.environ["VEXHIP_PLANE_FORCE"] = "1"
+        for k, v in (("VEXHIP_PLANE_STORE", store), ("VEXHIP_PLANE_TILE", tile)):
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+        A = T.ops.SpMat(T.up(ptr), T.up(col), T.up(val))
+        assert A.product == product, (name, store, A.product, A.reason)
+        if name.startswith("f64-plane"):
+            assert A.plane["tile"] == (tile or 2) and A.plane["flat"] == (1 if name == "f64-plane-flat" else 0), (name, A.plane)
+            assert A.plane["store_policy"] == ((2 if tile == 4 else 1) if store is None else store), (name, store, A.plane)
+        elif "grid" in name:
+            assert A.plane is None and (A.grid["threads"] > 256) == (shape[0] > 512), (name, A.grid)      # (the plan's lanes are the fp64 kernel's)
+            assert A.grid["store_policy"] == (1 if store is None else store), (name, store, A.grid)
+        dx = T.up(x)
+        for alpha, beta in _STORE_ALPHA_BETA:
+            dy = T.up(np.full(m, np.nan, dtype=vt)); A.apply(dx, dy, alpha, False)
+            assert np.array_equal(dy.cpu().numpy(), ax[alpha]), (name, store, alpha, "=")
+            dy = T.up(y0); A.apply(dx, dy, alpha, True)
+            assert np.array_equal(dy.cpu().numpy(), y0 + ax[alpha]), (name, store, alpha, "+=")
+            dy = T.up(np.full(m, np.nan, dtype=vt)); A.apply_axpby(dx, dy, alpha, T.up(z), beta)
+            assert np.array_equal(dy.cpu().numpy(), vt(beta) * z + ax[alpha]), (name, store, alpha, beta, "z")
+            dy = T.up(np.full(m, np.nan, dtype=vt)); A.apply_axpby(dx, dy, alpha, dx, beta)
+            assert np.array_equal(dy.cpu().numpy(), vt(beta) * x + ax[alpha]), (name, store, alpha, beta, "z = x")
+            dy = T.up(y0); A.apply_axpby(dx, dy, alpha, dy, beta)
+            assert np.array_equal(dy.cpu().numpy(), vt(beta) * y0 + ax[alpha]), (name, store, alpha, beta, "z = y")
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 def _fused(T, built_lib, A, m):
     v = T.torch.zeros(m, dtype=A.dtype, device=T.dev)
     return bool(built_lib.spmat_axpby_fused(A.handle, T.ops._p(v), T.ops._p(v), T.ops._p(T.torch.zeros_like(v))))

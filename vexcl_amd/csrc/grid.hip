@@ -1233,77 +1233,45 @@ int vexhip_spmv_sell8v_grid_f64(int dev, void *stream, int64_t n, double alpha, 
 } // extern "C"
 
 namespace vexhip {
-// y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the grid product (spmat.hip vexhip_spmat_apply_axpby_f64)
-int grid_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, const double *values,
-        const double *x, double *y, const vexhip_grid *g)
+// the two launches below: the product on a matrix of n rows, or (HALO; else H is not looked at) one device's step, which has '=' and '+=' only
+template <bool HALO>
+static int grid_run(int dev, hipStream_t s, int64_t n, double alpha, int zm, const double *zs, double beta, const double *values, const double *x, double *y,
+        const vexhip_grid *g, const halo_dev &H)
 {
-    VEXHIP_REQUIRE(g && g->usable && g->line_class && g->table && values && x && y, "bad grid product arguments");
-    if (int rc = vexhip_sell8_grid_check(g, n)) return rc;
-    VEXHIP_REQUIRE(g->x_last + 1 >= n, "bad grid plan");
+    if (int rc = grid_check(g, n, values, x, y, !HALO)) return rc;
     VEXHIP_REQUIRE((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0, "grid product: x and y must be 8-byte aligned");
-    VEXHIP_REQUIRE(zm == 0 || zm == 2 || (zm == 1 && zs && (reinterpret_cast<uintptr_t>(zs) & 7) == 0), "grid product: the addend must be an 8-byte aligned vector");
+    if (HALO) { if (int rc = check_halo_step(H, g->planes, (long long)g->lines_per_plane * g->nx, true)) return rc; }
+    VEXHIP_REQUIRE(zm == 0 || (zm == 2 && !HALO) || (zm == 1 && zs && (reinterpret_cast<uintptr_t>(zs) & 7) == 0), "grid product: the addend must be an 8-byte aligned vector");
     VEXHIP_SET_DEVICE(dev);
-    grid_dev gd;
-    gd.lines = n / g->nx; gd.x_last = g->x_last; gd.n = n;
-    gd.nx = g->nx; gd.ny = g->lines_per_plane; gd.nz = g->planes; gd.depth = g->depth;
-    gd.segs = g->segments; gd.seg_len = g->segment_rows;
-    gd.tiles = (gd.ny + 1) / 2 * gd.segs; gd.tpx = (gd.tiles + 7) / 8; gd.hot = g->hot_class; gd.pitch = g->pitch; gd.flat = g->flat;
-    const long long chunks = (gd.nz + gd.depth - 1) / gd.depth;
-    gd.cpx = gd.flat ? (int)((chunks + 7) / 8) : 0;
-    const long long grid = gd.cpx ? 8ll * gd.cpx * gd.tiles : 8ll * gd.tpx * chunks;
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
+    grid_dev gd = grid_launch(*g, n);
+    // a step: the walks are the plan's (chosen for the balance of the CUs, grid_geometry_with: shorter ones cost more than the wait they would
+    // save -- a strip of 640^3 / 8 in walks of 20 planes took 170 us against 125 us in the plan's, profiles/r06_dist_step_f64_640_first.json)
+    const int planes = HALO ? H.z1 - H.z0 : gd.nz;
+    if (HALO) gd.depth = std::min(gd.depth, planes);
+    unsigned grid;
+    if (int rc = grid_workgroups(gd, planes, &grid)) return rc;
+    const long long off = HALO ? (long long)H.z0 * gd.ny * gd.nx : 0;      // a step: the kernel addresses x and y in the numbering of the stored grid
     const unsigned char *tb = static_cast<const unsigned char *>(g->table);
-    hipStream_t s = as_stream(stream);
-    const halo_dev none = halo_dev();
-#define GRID_LAUNCH(AP, AUX) { if (g->threads > 256) sell8_grid_kernel<AP, AUX, 512><<<(unsigned)grid, (unsigned)g->threads, 0, s>>>(x, y, alpha, zs, beta, g->line_class, tb, values, gd, none); \
-                               else sell8_grid_kernel<AP, AUX, 256><<<(unsigned)grid, (unsigned)g->threads, 0, s>>>(x, y, alpha, zs, beta, g->line_class, tb, values, gd, none); }
-#define GRID_AUX(AP) switch (g->store_policy) { case 1: GRID_LAUNCH(AP, 18); break; case 2: GRID_LAUNCH(AP, 17); break; case 3: GRID_LAUNCH(AP, 0); break; default: GRID_LAUNCH(AP, 2); }
-    if (zm == 1) { GRID_AUX(1) } else if (zm == 2) { GRID_AUX(2) } else { GRID_AUX(0) }
-#undef GRID_AUX
-#undef GRID_LAUNCH
+    with_launch_forms(zm, g->store_policy, [&](auto ZM, auto AUX) {          // (the policy was read when the plan was made: grid_fill_plan)
+        if constexpr (!HALO || ZM() != 2) {
+            auto kernel = g->threads > 256 ? sell8_grid_kernel<ZM(), AUX(), 512, HALO> : sell8_grid_kernel<ZM(), AUX(), 256, HALO>;
+            kernel<<<grid, (unsigned)g->threads, 0, s>>>(x - off, y - off, alpha, zs ? zs - off : nullptr, beta, g->line_class, tb, values, gd, H);
+        }
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
 
+// y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the grid product (spmat.hip vexhip_spmat_apply_axpby_f64)
+int grid_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, const double *values,
+        const double *x, double *y, const vexhip_grid *g)
+{ return grid_run<false>(dev, as_stream(stream), n, alpha, zm, zs, beta, values, x, y, g, halo_dev()); }
 
 // One device's product step in one launch on a matrix stored by grid line with lines of ANY length (halo.hpp, the pull form): the
 // grid product over the planes [H.z0, H.z1) of the stored grid of n_ext rows; x and y are the device's own segments.
 int grid_apply_halo(int dev, hipStream_t s, int64_t n_ext, double alpha, int append, const double *values, const double *x, double *y,
         const vexhip_grid *g, halo_dev H)
-{
-    VEXHIP_REQUIRE(g && g->usable && g->line_class && g->table && values && x && y, "bad grid product arguments");
-    if (int rc = vexhip_sell8_grid_check(g, n_ext)) return rc;
-    VEXHIP_REQUIRE(H.pull && H.z0 >= 0 && H.z1 > H.z0 && H.z1 <= g->planes && H.step && H.done && H.err, "bad halo step");
-    VEXHIP_REQUIRE((long long)H.halo == (long long)g->lines_per_plane * g->nx, "the ghost planes must be planes of the stored grid");
-    VEXHIP_REQUIRE((!H.lo || H.z0 >= 1) && (!H.hi || H.z1 < g->planes), "a ghost plane outside the stored grid");
-    VEXHIP_REQUIRE((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0, "grid product: x and y must be 8-byte aligned");
-    VEXHIP_SET_DEVICE(dev);
-    grid_dev gd;
-    gd.lines = n_ext / g->nx; gd.x_last = g->x_last; gd.n = n_ext;
-    gd.nx = g->nx; gd.ny = g->lines_per_plane; gd.nz = g->planes; gd.depth = g->depth;
-    gd.segs = g->segments; gd.seg_len = g->segment_rows;
-    gd.tiles = (gd.ny + 1) / 2 * gd.segs; gd.tpx = (gd.tiles + 7) / 8; gd.hot = g->hot_class; gd.pitch = g->pitch; gd.flat = g->flat;
-    // the walks are the plan's (chosen for the balance of the CUs, grid_geometry_with: shorter ones cost more than the wait they would
-    // save -- a strip of 640^3 / 8 in walks of 20 planes took 170 us against 125 us in the plan's, profiles/r06_dist_step_f64_640_first.json)
-    const int nzr = H.z1 - H.z0;
-    gd.depth = std::min(gd.depth, nzr);
-    const long long chunks = (nzr + gd.depth - 1) / gd.depth;
-    gd.cpx = gd.flat ? (int)((chunks + 7) / 8) : 0;
-    const long long grid = gd.cpx ? 8ll * gd.cpx * gd.tiles : 8ll * gd.tpx * chunks;
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-    const long long plane = (long long)gd.ny * gd.nx;
-    const double *xe = x - (long long)H.z0 * plane;            // the kernel addresses x and y in the numbering of the stored grid
-    double *ye = y - (long long)H.z0 * plane;
-    const unsigned char *tb = static_cast<const unsigned char *>(g->table);
-#define GRID_HLAUNCH(AP, AUX) { if (g->threads > 256) sell8_grid_kernel<AP, AUX, 512, true><<<(unsigned)grid, (unsigned)g->threads, 0, s>>>(xe, ye, alpha, ye, 1.0, g->line_class, tb, values, gd, H); \
-                                else sell8_grid_kernel<AP, AUX, 256, true><<<(unsigned)grid, (unsigned)g->threads, 0, s>>>(xe, ye, alpha, ye, 1.0, g->line_class, tb, values, gd, H); }
-#define GRID_HAUX(AP) switch (g->store_policy) { case 1: GRID_HLAUNCH(AP, 18); break; case 2: GRID_HLAUNCH(AP, 17); break; case 3: GRID_HLAUNCH(AP, 0); break; default: GRID_HLAUNCH(AP, 2); }
-    if (append) { GRID_HAUX(1) } else { GRID_HAUX(0) }
-#undef GRID_HAUX
-#undef GRID_HLAUNCH
-    VEXHIP_LAUNCH_CHECK();
-    return 0;
-}
+{ return grid_run<true>(dev, s, n_ext, alpha, append ? 1 : 0, y, 1.0, values, x, y, g, H); }
 } // namespace vexhip
 
 VEXHIP_WARM_TU(grid)

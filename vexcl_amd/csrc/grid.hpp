@@ -1,5 +1,7 @@
-// What the grid products share (grid.hip: fp64, two rows per lane; grid32.hip: fp32, four rows per lane): the geometry a launch is given.
+// What the grid products share (grid.hip: fp64, two rows per lane; grid32.hip: fp32, four rows per lane): the geometry a launch is given
+// and how the host assembles it.
 #pragma once
+#include "launch.hpp"
 
 namespace vexhip {
 namespace {
@@ -19,6 +21,35 @@ struct grid_dev {
                              // a row of a 2-D grid has a handful of tiles -- six for 12 000 points -- and nothing to share between them): an XCD
                              // owns cpx consecutive WALKS of every tile, blockIdx -> (xcd, walk, tile)
 };
+
+// The requirements of a launch on a matrix of `rows` rows.  whole_x: the plan's x_last must cover the rows (false: a one-launch step, whose x is
+// the device's segment)
+inline int grid_check(const vexhip_grid *g, int64_t rows, const void *values, const void *x, const void *y, bool whole_x) {
+    VEXHIP_REQUIRE(g && g->usable && g->line_class && g->table && values && x && y, "bad grid product arguments");
+    if (int rc = vexhip_sell8_grid_check(g, rows)) return rc;
+    VEXHIP_REQUIRE(!whole_x || g->x_last + 1 >= rows, "bad grid plan");
+    return 0;
+}
+
+// the launch struct of a plan with the plan's walks (cpx: grid_workgroups); rows: those the launch addresses (a one-launch step: of the stored grid)
+inline grid_dev grid_launch(const vexhip_grid &g, long long rows) {
+    grid_dev gd;
+    gd.lines = rows / g.nx; gd.x_last = g.x_last; gd.n = rows;
+    gd.nx = g.nx; gd.ny = g.lines_per_plane; gd.nz = g.planes; gd.depth = g.depth;
+    gd.segs = g.segments; gd.seg_len = g.segment_rows;
+    gd.tiles = (gd.ny + 1) / 2 * gd.segs; gd.tpx = (gd.tiles + 7) / 8; gd.hot = g.hot_class; gd.pitch = g.pitch; gd.flat = g.flat;
+    return gd;
+}
+
+// Workgroups of a launch that walks `planes` planes gd.depth at a time, and who owns what (gd.cpx: see above)
+inline int grid_workgroups(grid_dev &gd, long long planes, unsigned *grid) {
+    const long long chunks = (planes + gd.depth - 1) / gd.depth;
+    gd.cpx = gd.flat ? (int)((chunks + 7) / 8) : 0;
+    const long long n = gd.cpx ? 8ll * gd.cpx * gd.tiles : 8ll * gd.tpx * chunks;
+    VEXHIP_REQUIRE(n < (1ll << 31), "matrix too large for one launch");
+    *grid = (unsigned)n;
+    return 0;
+}
 
 } // namespace
 } // namespace vexhip

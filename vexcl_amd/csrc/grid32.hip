@@ -287,63 +287,54 @@ int vexhip_spmv_sell8v_grid_f32(int dev, void *stream, int64_t n, float alpha, i
 } // extern "C"
 
 namespace vexhip {
+// Planes per workgroup of the fp32 grid product (host arithmetic only) for workgroups of `threads` lanes on `tiles` tiles and nz planes.
+// A workgroup is 1 .. 4 waves (four rows per lane) and a CU holds eight waves of this kernel.  Measured (ms by walk depth,
+// profiles/r05_fp32_sizes.json): the best launch is ONE round of workgroups that just fills the CUs -- 384^3 (192 tiles x 2 waves)
+// 96 / 77 / 64 / 48 planes = 0.120 / 0.103 / 0.136 / 0.115 (3 / 3.75 / 4.5 / 6 workgroups per CU), 500^3 125 / 100 / 63 = 0.217 /
+// 0.304 / 0.228 (3.9 / 4.9 / 7.8), 512^3 128 / 86 / 64 = 0.214 / 0.244 / 0.259 (4 / 6 / 8) -- a little more than one round is the
+// worst.  Workgroups of three and four waves (two per CU, 1.25 .. 2 tiles per CU) cannot do that: many short walks, at least
+// eight per CU, as the fp64 grid product does it (640^3: 320 / 160 / 80 planes = 0.697 / 0.595 / 0.524).
+static long long grid32_depth(long long cus, long long tiles, int threads, long long nz)
+{
+    const long long resident = std::max(1, 8 / (threads / 64));
+    const long long cmax = std::max(1ll, nz / 16);
+    long long chunks = std::min(cmax, resident * cus / tiles);
+    if (resident < 3 || chunks < 1 || tiles * chunks * 20 < resident * cus * 17) {
+        double best = 0;
+        chunks = 1;
+        for (long long c = 1; c <= cmax; ++c) {
+            const long long per_cu = (tiles * c + cus - 1) / cus;
+            if (per_cu < 8 && c < cmax) continue;
+            const double est = (double)per_cu * (double)((nz + c - 1) / c + 6);
+            if (best == 0 || est < best) { best = est; chunks = c; }
+            if (per_cu > 24) break;
+        }
+    }
+    return (nz + chunks - 1) / chunks;
+}
+
 // y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the fp32 grid product (spmat.hip vexhip_spmat_apply_axpby_f32)
 int grid_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, const float *values,
         const float *x, float *y, const vexhip_grid *g)
 {
-    VEXHIP_REQUIRE(g && g->usable && g->line_class && g->table && values && x && y, "bad grid product arguments");
-    if (int rc = vexhip_sell8_grid_check(g, n)) return rc;
-    VEXHIP_REQUIRE(g->x_last + 1 >= n, "bad grid plan");
+    if (int rc = grid_check(g, n, values, x, y, true)) return rc;
+    VEXHIP_REQUIRE(zm == 0 || zm == 2 || (zm == 1 && zs), "grid product: the addend must be a vector");
     VEXHIP_SET_DEVICE(dev);
-    grid_dev gd;
-    gd.lines = n / g->nx; gd.x_last = g->x_last; gd.n = n;
-    gd.nx = g->nx; gd.ny = g->lines_per_plane; gd.nz = g->planes;
-    gd.segs = g->segments; gd.seg_len = g->segment_rows;
-    gd.tiles = (gd.ny + 1) / 2 * gd.segs; gd.tpx = (gd.tiles + 7) / 8; gd.hot = g->hot_class; gd.pitch = g->pitch; gd.flat = g->flat;
-    // A workgroup is 1 .. 4 waves (four rows per lane) and a CU holds eight waves of this kernel.  Measured (ms by walk depth,
-    // profiles/r05_fp32_sizes.json): the best launch is ONE round of workgroups that just fills the CUs -- 384^3 (192 tiles x 2 waves)
-    // 96 / 77 / 64 / 48 planes = 0.120 / 0.103 / 0.136 / 0.115 (3 / 3.75 / 4.5 / 6 workgroups per CU), 500^3 125 / 100 / 63 = 0.217 /
-    // 0.304 / 0.228 (3.9 / 4.9 / 7.8), 512^3 128 / 86 / 64 = 0.214 / 0.244 / 0.259 (4 / 6 / 8) -- a little more than one round is the
-    // worst.  Workgroups of three and four waves (two per CU, 1.25 .. 2 tiles per CU) cannot do that: many short walks, at least
-    // eight per CU, as the fp64 grid product does it (640^3: 320 / 160 / 80 planes = 0.697 / 0.595 / 0.524).
+    grid_dev gd = grid_launch(*g, n);
     const int threads = std::max(64, std::min(G32_MAXT, ((g->segment_rows + 3) / 4 + 63) / 64 * 64));
-    {
-        const long long cus = std::max(1, info(dev).cus);
-        const long long resident = std::max(1, 8 / (threads / 64));
-        const long long cmax = std::max(1ll, (long long)gd.nz / 16);
-        long long chunks = std::min(cmax, resident * cus / gd.tiles);
-        if (resident < 3 || chunks < 1 || gd.tiles * chunks * 20 < resident * cus * 17) {
-            double best = 0;
-            chunks = 1;
-            for (long long c = 1; c <= cmax; ++c) {
-                const long long per_cu = (gd.tiles * c + cus - 1) / cus;
-                if (per_cu < 8 && c < cmax) continue;
-                const double est = (double)per_cu * (double)((gd.nz + c - 1) / c + 6);
-                if (best == 0 || est < best) { best = est; chunks = c; }
-                if (per_cu > 24) break;
-            }
-        }
-        gd.depth = (int)((gd.nz + chunks - 1) / chunks);
-    }
+    gd.depth = (int)grid32_depth(std::max(1, info(dev).cus), gd.tiles, threads, gd.nz);       // this product's own walks, not the plan's (the fp64 kernel's)
     if (const char *e = env(ENV_VEXHIP_GRID32_DEPTH)) if (std::atoi(e) > 0) gd.depth = std::min(std::atoi(e), (int)gd.nz);
     VEXHIP_REQUIRE(((long long)gd.depth + 4) * gd.ny * gd.nx * 4 < (1ll << 32), "bad grid plan");
-    const long long chunks = (gd.nz + gd.depth - 1) / gd.depth;
-    gd.cpx = gd.flat ? (int)((chunks + 7) / 8) : 0;
-    const long long grid = gd.cpx ? 8ll * gd.cpx * gd.tiles : 8ll * gd.tpx * chunks;
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
+    unsigned grid;
+    if (int rc = grid_workgroups(gd, gd.nz, &grid)) return rc;
     const unsigned char *tb = static_cast<const unsigned char *>(g->table);
-    hipStream_t s = as_stream(stream);
-#define G32_LAUNCH(AP, AUX) sell8_grid_f32_kernel<AP, AUX><<<(unsigned)grid, (unsigned)threads, 0, s>>>(x, y, alpha, zs, beta, g->line_class, tb, values, gd)
-#define G32_AUX(AP) switch (g->store_policy) { case 1: G32_LAUNCH(AP, 18); break; case 2: G32_LAUNCH(AP, 17); break; case 3: G32_LAUNCH(AP, 0); break; default: G32_LAUNCH(AP, 2); }
-    VEXHIP_REQUIRE(zm == 0 || zm == 2 || (zm == 1 && zs), "grid product: the addend must be a vector");
-    if (zm == 1) { G32_AUX(1) } else if (zm == 2) { G32_AUX(2) } else { G32_AUX(0) }
-#undef G32_AUX
-#undef G32_LAUNCH
+    with_launch_forms(zm, g->store_policy, [&](auto ZM, auto AUX) {       // (the policy was read when the plan was made: grid.hip grid_fill_plan)
+        sell8_grid_f32_kernel<ZM(), AUX()><<<grid, (unsigned)threads, 0, as_stream(stream)>>>(x, y, alpha, zs, beta, g->line_class, tb, values, gd);
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
 
 } // namespace vexhip
-
 
 VEXHIP_WARM_TU(grid32)

@@ -515,38 +515,17 @@ namespace vexhip {
 int plane_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, int64_t w, const void *pool,
         const int32_t *blocks, const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane)
 {
-    VEXHIP_REQUIRE(plane && plane->usable && pool && blocks && deltas && values && x && y, "bad plane product arguments");
-    VEXHIP_REQUIRE(n > 0 && n % PL_ROWS == 0 && w >= 1 && w <= 8, "bad plane product geometry");
-    VEXHIP_REQUIRE(plane->table_pitch == 0 || plane->table_pitch >= PL_ROWS + 2, "bad plane plan (table pitch)");
-    VEXHIP_REQUIRE((plane->tile == 2 || plane->tile == 4) && plane->lines_per_plane >= 4 && plane->lines_per_plane % plane->tile == 0 && plane->depth >= 1 && plane->planes >= 1
-                   && (plane->x_last + 1) % PL_ROWS == 0
-                   && ((long long)plane->depth + 4) * plane->lines_per_plane * 4096 < (1ll << 32), "bad plane plan");
-    VEXHIP_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0, "plane product: x and y must be 16-byte aligned");
+    if (int rc = plane_check(plane, 0, 4096, n, w, pool && blocks && deltas && values, x, y, true)) return rc;      // the plan's tile, the plan's depth
     VEXHIP_REQUIRE(zm == 0 || zm == 2 || (zm == 1 && zs && (reinterpret_cast<uintptr_t>(zs) & 15) == 0), "plane product: the addend must be a 16-byte aligned vector");
     VEXHIP_SET_DEVICE(dev);
-    plane_dev pd;
-    pd.nslices = n / PL_ROWS; pd.xlines = (plane->x_last + 1) / PL_ROWS; pd.x_last = plane->x_last;
-    pd.ny = plane->lines_per_plane; pd.nz = plane->planes; pd.depth = plane->depth;
-    pd.tiles = pd.ny / plane->tile; pd.tpx = (pd.tiles + 7) / 8; pd.hot = plane->hot_block; pd.w = (int)w; pd.far = pd.ny * PL_ROWS;
-    pd.pitch = plane->table_pitch;
-    const long long chunks = (pd.nz + pd.depth - 1) / pd.depth;
-    const long long grid = 8ll * pd.tpx * chunks;
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-    const int store_kind = plane->store_policy;
+    const plane_dev pd = plane_launch(*plane, n, w, plane->tile, plane->depth);
+    unsigned grid;
+    if (int rc = plane_workgroups(pd, pd.nz, 0, 0, &grid)) return rc;
     const char *cpool = static_cast<const char *>(pool);
-    hipStream_t s = as_stream(stream);
-    const halo_dev none = halo_dev();
-#define PLANE_LAUNCH(TY, ZM, AUX) sell8_plane_kernel<TY, ZM, AUX><<<(unsigned)grid, 256, 0, s>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd, none)
-#define PLANE_AUX(TY, AP) switch (store_kind) { case 1: PLANE_LAUNCH(TY, AP, 18); break; case 2: PLANE_LAUNCH(TY, AP, 17); break; case 3: PLANE_LAUNCH(TY, AP, 0); break; default: PLANE_LAUNCH(TY, AP, 2); }
-#define PLANE_FLAT(ZM, AUX) sell8_plane_kernel<2, ZM, AUX, false, true><<<(unsigned)grid, 256, 0, s>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd, none)
-#define PLANE_FAUX(AP) switch (store_kind) { case 1: PLANE_FLAT(AP, 18); break; case 2: PLANE_FLAT(AP, 17); break; case 3: PLANE_FLAT(AP, 0); break; default: PLANE_FLAT(AP, 2); }
-    if (plane->tile == 4) { if (zm == 1) { PLANE_AUX(4, 1) } else if (zm == 2) { PLANE_AUX(4, 2) } else { PLANE_AUX(4, 0) } }
-    else if (plane->flat) { if (zm == 1) { PLANE_FAUX(1) } else if (zm == 2) { PLANE_FAUX(2) } else { PLANE_FAUX(0) } }
-    else { if (zm == 1) { PLANE_AUX(2, 1) } else if (zm == 2) { PLANE_AUX(2, 2) } else { PLANE_AUX(2, 0) } }
-#undef PLANE_FAUX
-#undef PLANE_FLAT
-#undef PLANE_AUX
-#undef PLANE_LAUNCH
+    with_launch_forms(zm, plane->store_policy, [&](auto ZM, auto AUX) {      // (the plan's policy: plane_geometry_with; the flat walk exists for tiles of two only)
+        auto kernel = plane->tile == 4 ? sell8_plane_kernel<4, ZM(), AUX()> : plane->flat ? sell8_plane_kernel<2, ZM(), AUX(), false, true> : sell8_plane_kernel<2, ZM(), AUX()>;
+        kernel<<<grid, 256, 0, as_stream(stream)>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd, halo_dev());
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -602,9 +581,7 @@ static bool plane_geometry_with(long long cus, long long ny, long long nz, int h
     while ((depth + 4) * ny * 4096 >= (1ll << 32) && depth > 8) depth = (depth + 1) / 2;      // 32-bit byte offsets inside a workgroup's walk
     if ((depth + 4) * ny * 4096 >= (1ll << 32)) return false;
     out->lines_per_plane = (int32_t)ny; out->planes = (int32_t)nz; out->depth = (int32_t)depth; out->hot_block = hot; out->tile = (int32_t)tile;
-    // Cache policy of the y stores: 0 = non-temporal, 1 = non-temporal + sc1, 2 = sc0 sc1 (write-through, the line leaves the L2:
-    // more of it is left for the halo lines of x), 3 = plain.  Same sweeps, tile 4 x 256: 0.395 / 0.393 / 0.384 / 0.387 ms;
-    // tile 2 x 512: 0.395 / 0.391 / 0.396 / 0.401.  VEXHIP_PLANE_STORE overrides.
+    // cache policy of the y stores (launch.hpp with_launch_forms: the policies and their measurements); VEXHIP_PLANE_STORE overrides
     out->store_policy = tile == 4 ? 2 : 1;
     if (const char *e = env(ENV_VEXHIP_PLANE_STORE)) out->store_policy = std::max(0, std::min(3, std::atoi(e)));
     return true;
@@ -638,20 +615,10 @@ namespace vexhip {
 int plane_apply_halo(int dev, hipStream_t s, int64_t n_ext, double alpha, int append, int64_t w, const void *pool, const int32_t *blocks,
         const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane, halo_dev H)
 {
-    VEXHIP_REQUIRE(plane && plane->usable && pool && blocks && deltas && values && x && y, "bad plane product arguments");
-    VEXHIP_REQUIRE(n_ext > 0 && n_ext % PL_ROWS == 0 && w >= 1 && w <= 8, "bad plane product geometry");
-    VEXHIP_REQUIRE(plane->lines_per_plane >= 4 && plane->lines_per_plane % 2 == 0 && plane->depth >= 1 && plane->planes >= 1
-                   && ((long long)plane->depth + 4) * plane->lines_per_plane * 4096 < (1ll << 32), "bad plane plan");
-    VEXHIP_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0, "plane product: x and y must be 16-byte aligned");
-    VEXHIP_REQUIRE(H.z0 >= 0 && H.z1 > H.z0 && H.z1 <= plane->planes && H.step && H.done && H.err && H.push_blocks >= 0, "bad halo step");
-    VEXHIP_REQUIRE(H.halo == plane->lines_per_plane * PL_ROWS, "the ghost planes must be planes of the stored grid");
-    VEXHIP_REQUIRE((!H.lo || H.z0 >= 1) && (!H.hi || H.z1 < plane->planes), "a ghost plane outside the stored grid");
+    // (the kernel of the step is the one for tiles of two lines whatever the plan's tile; the depth checked is the plan's, the one walked is chosen below)
+    if (int rc = plane_check(plane, 2, 4096, n_ext, w, pool && blocks && deltas && values, x, y, true)) return rc;
+    if (int rc = check_halo_step(H, plane->planes, (long long)plane->lines_per_plane * PL_ROWS, false)) return rc;
     VEXHIP_SET_DEVICE(dev);
-    plane_dev pd;
-    pd.nslices = n_ext / PL_ROWS; pd.xlines = (plane->x_last + 1) / PL_ROWS; pd.x_last = plane->x_last;
-    pd.ny = plane->lines_per_plane; pd.nz = plane->planes; pd.depth = plane->depth;
-    pd.tiles = pd.ny / 2; pd.tpx = (pd.tiles + 7) / 8; pd.hot = plane->hot_block; pd.w = (int)w; pd.far = pd.ny * PL_ROWS;
-    pd.pitch = plane->table_pitch;
     const int nzr = H.z1 - H.z0;
     int edge_planes = 8;
     if (const char *e = env(ENV_VEXHIP_HALO_EDGE_PLANES)) edge_planes = std::max(1, std::atoi(e));
@@ -661,19 +628,18 @@ int plane_apply_halo(int dev, hipStream_t s, int64_t n_ext, double alpha, int ap
     H.lo_planes = H.lo ? std::min(lo_planes, nzr) : 0;
     H.hi_planes = H.hi ? std::min(hi_planes, nzr - H.lo_planes) : 0;
     const int mid = nzr - H.lo_planes - H.hi_planes;
-    pd.depth = std::max(1, mid);          // ONE main chunk (two of 25 planes beside the short chunks: 88-90 us against 76 for the step)
-    if (const char *e = env(ENV_VEXHIP_HALO_DEPTH)) pd.depth = std::max(1, std::atoi(e));
-    const long long chunks = (H.lo_planes ? 1 : 0) + (H.hi_planes ? 1 : 0) + (mid + pd.depth - 1) / pd.depth;
+    int depth = std::max(1, mid);         // ONE main chunk (two of 25 planes beside the short chunks: 88-90 us against 76 for the step)
+    if (const char *e = env(ENV_VEXHIP_HALO_DEPTH)) depth = std::max(1, std::atoi(e));
+    const plane_dev pd = plane_launch(*plane, n_ext, w, 2, depth);
     const long long npush = H.pull ? 0 : (H.dst_lo ? H.push_blocks : 0) + (H.dst_hi ? H.push_blocks : 0);
-    const long long grid = npush + 8ll * pd.tpx * chunks;
-    VEXHIP_REQUIRE(H.pull || H.push_blocks > 0 || 8ll * pd.tpx * chunks >= 512 || !(H.dst_lo || H.dst_hi), "too few workgroups to push the boundary planes");
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-    // the kernel addresses x and y in the numbering of the stored grid
-    const double *xe = x - (long long)H.z0 * pd.far;
+    unsigned grid;
+    if (int rc = plane_workgroups(pd, mid, (H.lo_planes ? 1 : 0) + (H.hi_planes ? 1 : 0), npush, &grid)) return rc;
+    VEXHIP_REQUIRE(H.pull || H.push_blocks > 0 || grid - npush >= 512 || !(H.dst_lo || H.dst_hi), "too few workgroups to push the boundary planes");
+    const double *xe = x - (long long)H.z0 * pd.far;          // the kernel addresses x and y in the numbering of the stored grid
     double *ye = y - (long long)H.z0 * pd.far;
     const char *cpool = static_cast<const char *>(pool);
-    if (append) sell8_plane_kernel<2, 1, 18, true><<<(unsigned)grid, 256, 0, s>>>(xe, ye, alpha, ye, 1.0, blocks, cpool, deltas, values, pd, H);
-    else        sell8_plane_kernel<2, 0, 18, true><<<(unsigned)grid, 256, 0, s>>>(xe, ye, alpha, nullptr, 0.0, blocks, cpool, deltas, values, pd, H);
+    auto kernel = append ? sell8_plane_kernel<2, 1, 18, true> : sell8_plane_kernel<2, 0, 18, true>;      // '=' and '+=' only; the stores of a step always take policy 1 (immediate 18)
+    kernel<<<grid, 256, 0, s>>>(xe, ye, alpha, append ? ye : nullptr, append ? 1.0 : 0.0, blocks, cpool, deltas, values, pd, H);
     VEXHIP_LAUNCH_CHECK();
     if (H.pull != 2 && !H.one_launch) {   // (events: the host advances nothing on the device -- there are no flags to number; one_launch: the last workgroup has done it)
         halo_signal_kernel<<<1, 1, 0, s>>>(H);

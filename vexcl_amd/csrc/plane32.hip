@@ -362,77 +362,51 @@ int vexhip_spmv_sell8v_plane_f32_i32(int dev, void *stream, int64_t n, float alp
 } // extern "C"
 
 namespace vexhip {
-// y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the fp32 plane product (spmat.hip vexhip_spmat_apply_axpby_f32)
-int plane_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool,
-        const int32_t *blocks, const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane)
+// the two launches below: the product on a matrix of n rows, or (HALO; else H is not looked at) one device's step, which has '=' and '+=' only
+template <bool HALO>
+static int plane32_run(int dev, hipStream_t s, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool, const int32_t *blocks,
+        const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane, const halo_dev &H)
 {
-    VEXHIP_REQUIRE(plane && plane->usable && pool && blocks && deltas && values && x && y, "bad plane product arguments");
-    VEXHIP_REQUIRE(n > 0 && n % PL_ROWS == 0 && w >= 1 && w <= 8, "bad plane product geometry");
-    VEXHIP_REQUIRE(plane->table_pitch == 0 || plane->table_pitch >= PL_ROWS + 2, "bad plane plan (table pitch)");
-    VEXHIP_REQUIRE(plane->lines_per_plane >= 4 && plane->lines_per_plane % 2 == 0 && plane->depth >= 1 && plane->planes >= 1
-                   && (plane->x_last + 1) % PL_ROWS == 0, "bad plane plan");
     // (x and y may start at any element: 16-byte requests at 4-byte addresses are served, a matrix stored by grid line has no
     //  other product to fall back on)
+    if (int rc = plane_check(plane, 2, 0, n, w, pool && blocks && deltas && values, x, y, false)) return rc;
+    if (HALO) { if (int rc = check_halo_step(H, plane->planes, (long long)plane->lines_per_plane * PL_ROWS, true)) return rc; }
+    VEXHIP_REQUIRE(zm == 0 || (zm == 2 && !HALO) || (zm == 1 && zs), "plane product: the addend must be a vector");
     VEXHIP_SET_DEVICE(dev);
-    plane_dev pd;
-    pd.nslices = n / PL_ROWS; pd.xlines = (plane->x_last + 1) / PL_ROWS; pd.x_last = plane->x_last;
-    pd.ny = plane->lines_per_plane; pd.nz = plane->planes;
-    pd.tiles = pd.ny / 2;
-    pd.depth = (int)vexhip_sell8_plane_f32_depth(std::max(1, info(dev).cus), pd.ny, pd.nz);
-    VEXHIP_REQUIRE(pd.depth > 0, "fp32 plane product: a walk of this grid does not fit 32-bit byte offsets");
-    pd.tpx = (pd.tiles + 7) / 8; pd.hot = plane->hot_block; pd.w = (int)w; pd.far = pd.ny * PL_ROWS;
-    pd.pitch = plane->table_pitch;
-    const long long chunks = (pd.nz + pd.depth - 1) / pd.depth;
-    const long long grid = 8ll * pd.tpx * chunks;
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
+    const int planes = HALO ? H.z1 - H.z0 : plane->planes;      // the depth is chosen for the planes THIS launch walks
+    const int depth = (int)vexhip_sell8_plane_f32_depth(std::max(1, info(dev).cus), plane->lines_per_plane, planes);
+    VEXHIP_REQUIRE(depth > 0, "fp32 plane product: a walk of this grid does not fit 32-bit byte offsets");
+    const plane_dev pd = plane_launch(*plane, n, w, 2, depth);
+    unsigned grid;
+    if (int rc = plane_workgroups(pd, planes, 0, 0, &grid)) return rc;
+    const long long off = HALO ? (long long)H.z0 * pd.far : 0;      // a step: the kernel addresses x and y in the numbering of the stored grid
     const char *cpool = static_cast<const char *>(pool);
-    hipStream_t s = as_stream(stream);
-    int store_kind = 1;
-    if (const char *e = env(ENV_VEXHIP_PLANE_STORE)) store_kind = std::max(0, std::min(3, std::atoi(e)));
-    const halo_dev none = halo_dev();
-#define P32_LAUNCH(AP, AUX) sell8_plane_f32_kernel<AP, AUX><<<(unsigned)grid, P32_LANES, 0, s>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd, none)
-#define P32_AUX(AP) switch (store_kind) { case 1: P32_LAUNCH(AP, 18); break; case 2: P32_LAUNCH(AP, 17); break; case 3: P32_LAUNCH(AP, 0); break; default: P32_LAUNCH(AP, 2); }
-    VEXHIP_REQUIRE(zm == 0 || zm == 2 || (zm == 1 && zs), "plane product: the addend must be a vector");
-    if (zm == 1) { P32_AUX(1) } else if (zm == 2) { P32_AUX(2) } else { P32_AUX(0) }
-#undef P32_AUX
-#undef P32_LAUNCH
+    if constexpr (HALO) {       // '=' and '+=' only; the stores of a step always take policy 1 (immediate 18)
+        auto kernel = zm ? sell8_plane_f32_kernel<1, 18, true> : sell8_plane_f32_kernel<0, 18, true>;
+        kernel<<<grid, P32_LANES, 0, s>>>(x - off, y - off, alpha, zs ? zs - off : nullptr, beta, blocks, cpool, deltas, values, pd, H);
+    } else {
+        // VEXHIP_PLANE_STORE is read HERE, at the launch (the other three products read it when the plan is made); unset: policy 1, whatever
+        // the plan holds for the fp64 kernel
+        int store_kind = 1;
+        if (const char *e = env(ENV_VEXHIP_PLANE_STORE)) store_kind = std::max(0, std::min(3, std::atoi(e)));
+        with_launch_forms(zm, store_kind, [&](auto ZM, auto AUX) {
+            sell8_plane_f32_kernel<ZM(), AUX()><<<grid, P32_LANES, 0, s>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd, H);
+        });
+    }
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
 
+// y = alpha A x + [zm 1: beta zs | zm 2: beta x] through the fp32 plane product (spmat.hip vexhip_spmat_apply_axpby_f32)
+int plane_apply_axpby(int dev, void *stream, int64_t n, float alpha, int zm, const float *zs, float beta, int64_t w, const void *pool,
+        const int32_t *blocks, const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane)
+{ return plane32_run<false>(dev, as_stream(stream), n, alpha, zm, zs, beta, w, pool, blocks, deltas, values, x, y, plane, halo_dev()); }
 
 // One device's product step in one launch for a float matrix on 512-point lines (halo.hpp, the pull form): the fp32 plane product over
 // the planes [H.z0, H.z1) of the stored grid of n_ext rows; x and y are the device's own segments.
 int plane_apply_halo(int dev, hipStream_t s, int64_t n_ext, float alpha, int append, int64_t w, const void *pool, const int32_t *blocks,
         const int32_t *deltas, const float *values, const float *x, float *y, const vexhip_plane *plane, halo_dev H)
-{
-    VEXHIP_REQUIRE(plane && plane->usable && pool && blocks && deltas && values && x && y, "bad plane product arguments");
-    VEXHIP_REQUIRE(n_ext > 0 && n_ext % PL_ROWS == 0 && w >= 1 && w <= 8, "bad plane product geometry");
-    VEXHIP_REQUIRE(plane->lines_per_plane >= 4 && plane->lines_per_plane % 2 == 0 && plane->planes >= 1, "bad plane plan");
-    VEXHIP_REQUIRE(H.pull && H.z0 >= 0 && H.z1 > H.z0 && H.z1 <= plane->planes && H.step && H.done && H.err, "bad halo step");
-    VEXHIP_REQUIRE(H.halo == plane->lines_per_plane * PL_ROWS, "the ghost planes must be planes of the stored grid");
-    VEXHIP_REQUIRE((!H.lo || H.z0 >= 1) && (!H.hi || H.z1 < plane->planes), "a ghost plane outside the stored grid");
-    VEXHIP_SET_DEVICE(dev);
-    plane_dev pd;
-    pd.nslices = n_ext / PL_ROWS; pd.xlines = (plane->x_last + 1) / PL_ROWS; pd.x_last = plane->x_last;
-    pd.ny = plane->lines_per_plane; pd.nz = plane->planes;
-    pd.tiles = pd.ny / 2;
-    const int nzr = H.z1 - H.z0;
-    pd.depth = (int)vexhip_sell8_plane_f32_depth(std::max(1, info(dev).cus), pd.ny, nzr);
-    VEXHIP_REQUIRE(pd.depth > 0, "fp32 plane product: a walk of this grid does not fit 32-bit byte offsets");
-    pd.tpx = (pd.tiles + 7) / 8; pd.hot = plane->hot_block; pd.w = (int)w; pd.far = pd.ny * PL_ROWS;
-    pd.pitch = plane->table_pitch;
-    const long long chunks = (nzr + pd.depth - 1) / pd.depth;
-    const long long grid = 8ll * pd.tpx * chunks;
-    VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-    const float *xe = x - (long long)H.z0 * pd.far;            // the kernel addresses x and y in the numbering of the stored grid
-    float *ye = y - (long long)H.z0 * pd.far;
-    const char *cpool = static_cast<const char *>(pool);
-    if (append) sell8_plane_f32_kernel<1, 18, true><<<(unsigned)grid, P32_LANES, 0, s>>>(xe, ye, alpha, ye, 1.0f, blocks, cpool, deltas, values, pd, H);
-    else        sell8_plane_f32_kernel<0, 18, true><<<(unsigned)grid, P32_LANES, 0, s>>>(xe, ye, alpha, nullptr, 0.0f, blocks, cpool, deltas, values, pd, H);
-    VEXHIP_LAUNCH_CHECK();
-    return 0;
-}
+{ return plane32_run<true>(dev, s, n_ext, alpha, append ? 1 : 0, append ? y : nullptr, append ? 1.0f : 0.0f, w, pool, blocks, deltas, values, x, y, plane, H); }
 } // namespace vexhip
 
 VEXHIP_WARM_TU(plane32)
