@@ -2047,3 +2047,67 @@ def test_ccsr_to_csr_expansion(T):
     oc = torch.empty(nnz.value, dtype=torch.int32, device=T.dev); ov = torch.empty(nnz.value, dtype=torch.float64, device=T.dev)
     L.ccsr_to_csr_f64_i32(0, None, n, p(d(idx)), p(drow), p(dcol), p(dval), p(ptr), p(oc), p(ov), ctypes.byref(bad))
     assert bad.value == -1
+
+
+def test_every_unrolled_width_through_every_launcher(T, oracle, built_lib):
+    """The launchers of the SELL family turn the run-time ELL width into a template argument (csrc/dispatch.hpp); the pair kernels
+    take the width at compile time ONLY, so a wrong one is a wrong slice stride.  Banded matrices of every unrolled width (1..9), of
+    widths past every unrolled range (10, 12), with one value per diagonal (value codes) and with random values, fp64 and fp32,
+    `y =` and `y += alpha A x`, through every storage and product that dispatches on the width -- 32-bit columns, diagonal codes,
+    value codes (each under the pair and the per-entry variant), the default SpMat (slice dictionary, march plan), without march,
+    without dictionary, the pair kernels through the march entry (variant 2), the reference's hybrid ELL, two right-hand sides --
+    against the oracle's CSR loop, bit for bit.  80 slices and a ragged 81st: the library looks for a slice dictionary from 64 slices on
+    (spmat.hip make_dictionary; the march plan needs the dictionary), and the interior slices repeat.  A matrix with stored values wider
+    than 8 columns has no dictionary by that same rule, and the test says so."""
+    n = 80 * 512 + 77
+    diagonals = (0, 1, -1, 2, -2, 3, -3, 4, -4, 5, -5, 6)
+    alpha = -0.75
+
+    def under(variant, run):
+        T.L.spmv_sell8_set_variant(variant)
+        try:
+            run()
+        finally:
+            T.L.spmv_sell8_set_variant(0)
+
+    for w in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12):
+        for constant in (True, False):
+            for dtype in (np.float64, np.float32):
+                what = (w, "one value per diagonal" if constant else "random values", dtype.__name__)
+                ptr, col, val = _band(n, sorted(diagonals[:w]), 40 + w, dtype=dtype, constant=constant)
+                x = [(oracle.random_f64(50 + k, n) - 0.5).astype(dtype) for k in range(2)]
+                y0 = oracle.random_f64(60, n).astype(dtype)
+                want = [oracle.spmv_csr(ptr, col, val, xk) for xk in x]
+                want_app = [oracle.spmv_csr(ptr, col, val, xk, y0.copy(), alpha, True) for xk in x]
+                dp, dc, dv, dx = T.up(ptr), T.up(col), T.up(val), [T.up(xk) for xk in x]
+
+                def check(form, apply):
+                    for append in (False, True):
+                        y = T.up(y0.copy())
+                        apply(dx[0], y, alpha if append else 1.0, append)
+                        assert np.array_equal(y.cpu().numpy(), (want_app if append else want)[0]), what + (form, "+=" if append else "=")
+
+                for kw in ({"codes": False}, {"value_codes": False}, {}):
+                    S = T.ops.SlicedELL(dp, dc, dv, **kw)
+                    assert S.width == w and S.tail_nnz == 0, what + (kw, S.width)
+                    assert (S.deltas is None) == ("codes" in kw) and (S.values is not None) == (constant and not kw), what + (kw,)
+                    for variant in (0, 1):
+                        under(variant, lambda: check(("SlicedELL", kw, variant), S.mul))
+                    if w in (3, 4, 5, 7, 9):
+                        for append in (False, True):
+                            ys = [T.up(y0.copy()) for _ in x]
+                            S.mul_multi(dx, ys, alpha if append else 1.0, append)
+                            for k in range(2):
+                                assert np.array_equal(ys[k].cpu().numpy(), (want_app if append else want)[k]), what + ("mul_multi", kw, k, append)
+                A = T.ops.SpMat(dp, dc, dv)
+                assert A.hell.width == w and A.storage == ("sell8v" if constant else "sell8"), what + (A.storage,)
+                assert (A.dictionary_blocks > 0) if (constant or w <= 8) else (A.dictionary_blocks == 0), what + (A.dictionary_blocks,)
+                if constant and w <= 8:
+                    assert A.march is not None, what
+                check("SpMat", A.apply)
+                under(2, lambda: check("SpMat, variant 2", A.apply))
+                for kw in ({"march": False}, {"dictionary": False}, {"fmt": "hell"}):
+                    B = T.ops.SpMat(dp, dc, dv, **kw)
+                    assert B.hell.width == w and B.march is None, what + (kw,)
+                    assert "dictionary" not in kw or B.dictionary_blocks == 0, what + (kw,)
+                    check(("SpMat", kw), B.apply)

@@ -1,6 +1,7 @@
 // Shared host-side helpers for libvexhip.so (error capture, device guard).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -105,6 +106,19 @@ struct setup_trace {
                      std::chrono::duration<double, std::milli>(now - last).count(), std::chrono::duration<double, std::milli>(now - t0).count());
         last = now;
     }
+};
+
+// Device scratch of a host function, freed on every exit path (a VEXHIP_TRY that returns early included).  free_now(): before the function goes
+// on with host work or returns its verdict; release(): the buffer becomes the caller's (hipFree).
+template <typename T> struct dev_buf {
+    T *p = nullptr;
+    dev_buf() = default;
+    dev_buf(const dev_buf &) = delete;
+    dev_buf &operator=(const dev_buf &) = delete;
+    ~dev_buf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)); }
+    hipError_t free_now() { T *q = p; p = nullptr; return q ? hipFree(q) : hipSuccess; }
+    T *release() { T *r = p; p = nullptr; return r; }
 };
 
 // scan.hip: the scans that other files of the library run inside their own steps

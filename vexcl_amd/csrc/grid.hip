@@ -970,15 +970,6 @@ bool grid_diagonals(const std::vector<int> &table, long long rows, long long *nx
     return true;
 }
 
-template <typename T> struct dev_buf {       // device scratch of the plan, freed on every exit path
-    T *p = nullptr;
-    ~dev_buf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)); }
-    void free_now() { if (p) (void)hipFree(p); p = nullptr; }
-    T *release() { T *r = p; p = nullptr; return r; }
-};
-
-
 } // namespace
 
 // ---- host side of the direct build ----
@@ -1086,7 +1077,7 @@ int grid_build(int dev, void *stream, int64_t rows, const P *ptr, const int32_t 
     out->usable = 1;
     *ndeltas = nd; *nvalues = nv; *ell_width = h_ints[GBI_MAXLEN]; *x_last_out = x_last;
     trace.mark("  grid: tables");
-    d_probe.free_now(); d_ctl.free_now();
+    (void)d_probe.free_now(); (void)d_ctl.free_now();
     trace.mark("  grid: scratch freed");
     return 0;
 }

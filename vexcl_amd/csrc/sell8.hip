@@ -21,6 +21,7 @@
 #include "halo.hpp"
 #include "storage.hpp"
 #include "lanes.hpp"
+#include "dispatch.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -1550,11 +1551,10 @@ int march_launch(int dev, hipStream_t s, int64_t n, long long ns, V alpha, int a
     VEXHIP_REQUIRE(m->lo <= 0 && m->hi >= 0 && m->run >= 1 && m->nfar >= 0 && m->nfar <= 2, "bad march plan");
     const bool strips = tr && tr->grid_blocks > 0 && tr->chunk > 0;
     VEXHIP_REQUIRE(!strips || tr->chunk % m->run == 0, "march run does not divide the strip length");
-    const long long grid = strips ? tr->grid_blocks / m->run : (ns + m->run - 1) / m->run;
+    long long slices = 0;                                                  // (the strip form only: an explicit order never comes here, spmv_sell8v)
+    trav_dev t8 = attach(make_traversal(strips ? tr : nullptr, ns, &slices), add);   // y = alpha A x + beta z: the kernel is told by append == 2
+    const long long grid = strips ? slices / m->run : (ns + m->run - 1) / m->run;
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-    trav_dev t8 = {nullptr, 0, 0, 0};
-    if (strips) t8 = trav_dev{nullptr, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
-    t8 = attach(t8, add);                                                  // y = alpha A x + beta z: the kernel is told by append == 2
     if (t8.z) append = 2;
     const int lo_e = m->lo & ~1;                                           // window bounds on even elements (16-byte ring accesses)
     const long long span_b = march_span_bytes(m->lo, m->hi, (int)sizeof(V));
@@ -1564,12 +1564,12 @@ int march_launch(int dev, hipStream_t s, int64_t n, long long ns, V alpha, int a
     if (lds_floor > lds && lds_floor <= 64 * 1024) lds = lds_floor;
     const march_dev mp = {m->lo, m->hi, lo_e, (int)span_b, (int)(span_b + 2 * S8_ROWS * (long long)sizeof(V)), m->run, m->nfar, m->far[0], m->far[1], (long long)m->x_last};
     const march_cold<V> cold = {(long long)n, ns, deltas, values, cp, cc, cv, pool, t8};
-#define MARCH(W) case W: sell8_march_kernel<V, W><<<(unsigned)grid, 256, (size_t)lds, s>>>(cold, alpha, append, x, y, blocks, mp); break;
-    switch (w) {
-        MARCH(1) MARCH(2) MARCH(3) MARCH(4) MARCH(5) MARCH(6) MARCH(7) MARCH(8)
-        default: return fail(__FILE__, __LINE__, "march kernels cover ELL widths 1..8");
-    }
-#undef MARCH
+    bool covered = true;
+    with_width<8>(w, [&](auto W) {
+        if constexpr (W() == 0) covered = false;
+        else sell8_march_kernel<V, W()><<<(unsigned)grid, 256, (size_t)lds, s>>>(cold, alpha, append, x, y, blocks, mp);
+    });
+    VEXHIP_REQUIRE(covered, "march kernels cover ELL widths 1..8");
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1586,11 +1586,12 @@ int sell8_apply_halo_impl(int dev, hipStream_t s, long long own_rows, V alpha, i
     const long long grid = own_rows / S8_ROWS;
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     const char *b = static_cast<const char *>(buf), *pool = static_cast<const char *>(pool_);
-#define HP(W, VC, DICT) sell8_pair_halo_kernel<V, W, VC, DICT><<<(unsigned)grid, 256, 0, s>>>(own_rows, alpha, append, b, deltas, values, x, y, pool, blocks, H)
-#define HCASE(W) case W: if (vcoded) { if (blocks) HP(W, true, true); else HP(W, true, false); } else { if (blocks) HP(W, false, true); else HP(W, false, false); } break;
-    switch (w) { HCASE(1) HCASE(2) HCASE(3) HCASE(4) HCASE(5) HCASE(6) HCASE(7) HCASE(8) }
-#undef HCASE
-#undef HP
+    with_width<8>(w, [&](auto W) {
+        if constexpr (W() != 0)                                            // (1..8: required above)
+            with_bools(vcoded, blocks != nullptr, [&](auto VCODED, auto DICT) {
+                sell8_pair_halo_kernel<V, W(), VCODED(), DICT()><<<(unsigned)grid, 256, 0, s>>>(own_rows, alpha, append, b, deltas, values, x, y, pool, blocks, H);
+            });
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1618,6 +1619,68 @@ void strip_traversal(int64_t n, const std::vector<int> &table, const std::vector
     if (out->grid_blocks >= (1ll << 31)) std::memset(out, 0, sizeof(*out));
 }
 
+// What the fills of the two coded storages share.  Scratch: [counts of the table's diagonals: 256 x 8 bytes | info: [0] unused, [1] error flag,
+// [2] largest ELL column]; the largest column is uploaded where the caller knows it and searched for otherwise; fill(STAGED, grid, ns, counts, info)
+// launches the fill kernel; then the copies back, the verdict on the error flag (not_in_table: the caller's message) and the strip traversal.
+template <typename P, class Fill>
+int coded_fill(int dev, hipStream_t s, int64_t n, const P *ptr, const int *col, int64_t w, const int *deltas, int ndeltas, vexhip_traversal *trav,
+        int64_t known_max_col, int64_t *max_col, const char *not_in_table, Fill &&fill)
+{
+    VEXHIP_SET_DEVICE(dev);
+    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
+    dev_buf<unsigned long long> dcounts;
+    VEXHIP_TRY(dcounts.alloc(256 + 4 * sizeof(int) / sizeof(unsigned long long)));
+    int *dinfo = reinterpret_cast<int *>(dcounts.p + 256);
+    VEXHIP_TRY(hipMemsetAsync(dcounts.p, 0, sizeof(unsigned long long) * 256 + 2 * sizeof(int), s));
+    if (known_max_col >= 0) {                                               // (the fused analysis of this matrix found it)
+        const int known = (int)known_max_col;
+        VEXHIP_TRY(hipMemcpyAsync(dinfo + 2, &known, sizeof(int), hipMemcpyHostToDevice, s));
+        VEXHIP_TRY(hipStreamSynchronize(s));
+    } else {
+        VEXHIP_TRY(hipMemsetAsync(dinfo + 2, 0xff, sizeof(int), s));
+        ell_max_col_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, dinfo + 2);
+    }
+    with_bool(w <= 8, [&](auto STAGED) { fill(STAGED, grid_for(dev, ns * (S8_ROWS / 2)), ns, dcounts.p, dinfo); });
+    std::vector<unsigned long long> counts(256);
+    std::vector<int> table(ndeltas);
+    int hinfo[3] = {0, 0, -1};
+    VEXHIP_TRY(hipMemcpyAsync(counts.data(), dcounts.p, sizeof(unsigned long long) * 256, hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(hinfo, dinfo, sizeof(hinfo), hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(table.data(), deltas, sizeof(int) * ndeltas, hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipStreamSynchronize(s));
+    VEXHIP_TRY(dcounts.free_now());
+    if (max_col) *max_col = hinfo[2];
+    VEXHIP_REQUIRE(hinfo[1] == 0, not_in_table);
+    if (trav) strip_traversal(n, table, counts, trav);
+    return 0;
+}
+
+// A hash set collected on the device, copied to the host (HASH_SLOTS slots, `empty` where nothing is; count / overflow: the set's own info) ->
+// the table the kernels search: sorted, `pad` behind the last entry, 256 entries uploaded to table_dev; *entries = their number.  A set that is no
+// table's (overflow, more than max_entries, none) leaves *entries and table_dev as they are.
+template <typename T>
+int upload_table(hipStream_t s, const T *slots, T empty, T pad, int count, int overflow, int max_entries, const char *inconsistent, void *table_dev, int *entries)
+{
+    if (overflow != 0 || count > max_entries || count < 1) return 0;
+    std::vector<T> table;
+    for (int k = 0; k < HASH_SLOTS; ++k) if (slots[k] != empty) table.push_back(slots[k]);
+    std::sort(table.begin(), table.end());                                    // (values: by bit pattern, what the fill kernel searches)
+    if ((int)table.size() != count) return fail(__FILE__, __LINE__, inconsistent);
+    table.resize(256, pad);
+    VEXHIP_TRY(hipMemcpyAsync(table_dev, table.data(), sizeof(T) * 256, hipMemcpyHostToDevice, s));
+    VEXHIP_TRY(hipStreamSynchronize(s));
+    *entries = count;
+    return 0;
+}
+inline int upload_deltas(hipStream_t s, const int *set, int32_t *deltas, int *ndeltas) {      // set: HASH_SLOTS slots, count, overflow; codes 254 and 255 are padding
+    return upload_table<int>(s, set, EMPTY, INT_MAX, set[HASH_SLOTS], set[HASH_SLOTS + 1], 254, "diagonal set is inconsistent", deltas, ndeltas);
+}
+template <typename V>
+int upload_values(hipStream_t s, const typename bits_of<V>::type *set, const int (&info)[2], V *values, int *nvalues) {    // 0.0 behind the last value: code 255 reads it
+    typedef typename bits_of<V>::type B;
+    return upload_table<B>(s, set, ~B(0), B(0), info[0], info[1], 255, "value set is inconsistent", values, nvalues);
+}
+
 } // namespace
 
 // ---- the typed set-up steps and products (storage.hpp) ----
@@ -1629,39 +1692,11 @@ int sell8_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, c
     if (trav) std::memset(trav, 0, sizeof(*trav));
     if (n == 0) return 0;
     VEXHIP_REQUIRE(ptr && col && val && deltas && buf, "NULL argument");
-    VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
-    unsigned long long *dcounts = nullptr;
-    VEXHIP_TRY(hipMalloc(&dcounts, sizeof(unsigned long long) * 256 + 4 * sizeof(int)));
-    int *dinfo = reinterpret_cast<int *>(dcounts + 256);                    // [0] unused, [1] error flag, [2] largest ELL column
-    VEXHIP_TRY(hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * 256 + 2 * sizeof(int), s));
-    if (known_max_col >= 0) {                                               // (the fused analysis of this matrix found it)
-        const int known = (int)known_max_col;
-        VEXHIP_TRY(hipMemcpyAsync(dinfo + 2, &known, sizeof(int), hipMemcpyHostToDevice, s));
-        VEXHIP_TRY(hipStreamSynchronize(s));
-    } else {
-        VEXHIP_TRY(hipMemsetAsync(dinfo + 2, 0xff, sizeof(int), s));
-        ell_max_col_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, dinfo + 2);
-    }
-    if (w <= 8)
-        sell8_fill_kernel<V, P, true><<<grid_for(dev, ns * (S8_ROWS / 2)), 256, 0, s>>>(n, ns, (int)w, ndeltas, ptr, col, val, deltas,
-                dinfo + 2, static_cast<char *>(buf), dcounts, dinfo);
-    else
-        sell8_fill_kernel<V, P, false><<<grid_for(dev, ns * (S8_ROWS / 2)), 256, 0, s>>>(n, ns, (int)w, ndeltas, ptr, col, val, deltas,
-                dinfo + 2, static_cast<char *>(buf), dcounts, dinfo);
-    std::vector<unsigned long long> counts(256);
-    std::vector<int> table(ndeltas);
-    int hinfo[3] = {0, 0, -1};
-    VEXHIP_TRY(hipMemcpyAsync(counts.data(), dcounts, sizeof(unsigned long long) * 256, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(hinfo, dinfo, sizeof(hinfo), hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(table.data(), deltas, sizeof(int) * ndeltas, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipStreamSynchronize(s));
-    VEXHIP_TRY(hipFree(dcounts));
-    if (max_col) *max_col = hinfo[2];
-    VEXHIP_REQUIRE(hinfo[1] == 0, "SELL8 fill: the matrix uses a diagonal that is not in the table");
-    if (trav) strip_traversal(n, table, counts, trav);
-    return 0;
+    return coded_fill(dev, s, n, ptr, col, w, deltas, ndeltas, trav, known_max_col, max_col, "SELL8 fill: the matrix uses a diagonal that is not in the table",
+            [&](auto STAGED, int grid, long long ns, unsigned long long *dcounts, int *dinfo) {
+                sell8_fill_kernel<V, P, STAGED()><<<grid, 256, 0, s>>>(n, ns, (int)w, ndeltas, ptr, col, val, deltas, dinfo + 2, static_cast<char *>(buf), dcounts, dinfo);
+            });
 }
 
 template <typename V>
@@ -1676,22 +1711,21 @@ int spmv_sell8(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
     const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
-    const bool ordered = tr && tr->grid_blocks > 0;
-    const long long grid = ordered ? tr->grid_blocks : ns;
-    trav_dev t8 = {nullptr, 0, 0, 0};
-    if (ordered) t8 = trav_dev{tr->order, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
-    t8 = attach(t8, add);                                          // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
+    long long grid = 0;
+    const trav_dev t8 = attach(make_traversal(tr, ns, &grid), add);  // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     const char *b = static_cast<const char *>(buf), *pool = static_cast<const char *>(pool_);
-#define PAIR(W, DICT) sell8_pair_kernel<V, W, false, DICT><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, b, deltas, (const V *)nullptr, cp, cc, cv, x, y, t8, pool, blocks)
-#define CASE(W) case W: if (g_sell8_variant != 1) { if (blocks) PAIR(W, true); else PAIR(W, false); } \
-        else sell8_kernel<V, W><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, cp, cc, cv, x, y, t8, pool, blocks); break;
-    switch (w) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-        default: sell8_kernel<V, 0><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, cp, cc, cv, x, y, t8, pool, blocks);
-    }
-#undef CASE
-#undef PAIR
+    const bool pairs = g_sell8_variant != 1;
+    with_width<8>((int)w, [&](auto W) {
+        if constexpr (W() != 0)
+            if (pairs) {
+                with_bool(blocks != nullptr, [&](auto DICT) {
+                    sell8_pair_kernel<V, W(), false, DICT()><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, b, deltas, (const V *)nullptr, cp, cc, cv, x, y, t8, pool, blocks);
+                });
+                return;
+            }
+        sell8_kernel<V, W()><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, cp, cc, cv, x, y, t8, pool, blocks);
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1705,29 +1739,20 @@ int sell8v_analyze(int dev, void *stream, int64_t n, const P *ptr, const V *val,
     if (n <= 0 || w < 1) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    B *d = nullptr;
-    VEXHIP_TRY(hipMalloc(&d, sizeof(B) * HASH_SLOTS + 2 * sizeof(int)));
-    int *dinfo = reinterpret_cast<int *>(d + HASH_SLOTS);
-    VEXHIP_TRY(hipMemsetAsync(d, 0xff, sizeof(B) * HASH_SLOTS, s));
+    dev_buf<char> d;
+    VEXHIP_TRY(d.alloc(sizeof(B) * HASH_SLOTS + 2 * sizeof(int)));
+    B *dset = reinterpret_cast<B *>(d.p);
+    int *dinfo = reinterpret_cast<int *>(dset + HASH_SLOTS);
+    VEXHIP_TRY(hipMemsetAsync(dset, 0xff, sizeof(B) * HASH_SLOTS, s));
     VEXHIP_TRY(hipMemsetAsync(dinfo, 0, 2 * sizeof(int), s));
-    value_collect_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, val, d, dinfo);
+    value_collect_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, val, dset, dinfo);
     std::vector<B> host(HASH_SLOTS);
     int hinfo[2] = {0, 0};
-    VEXHIP_TRY(hipMemcpyAsync(host.data(), d, sizeof(B) * HASH_SLOTS, hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(host.data(), dset, sizeof(B) * HASH_SLOTS, hipMemcpyDeviceToHost, s));
     VEXHIP_TRY(hipMemcpyAsync(hinfo, dinfo, sizeof(hinfo), hipMemcpyDeviceToHost, s));
     VEXHIP_TRY(hipStreamSynchronize(s));
-    VEXHIP_TRY(hipFree(d));
-    if (hinfo[1] != 0 || hinfo[0] > 255 || hinfo[0] < 1) return 0;          // too many distinct values: keep them as they are
-    std::vector<B> table;
-    for (B b : host) if (b != ~B(0)) table.push_back(b);
-    std::sort(table.begin(), table.end());                                    // sorted by bit pattern (what the fill kernel searches)
-    if ((int)table.size() != hinfo[0]) return fail(__FILE__, __LINE__, "value set is inconsistent");
-    std::vector<V> vals(256, V(0));
-    for (size_t k = 0; k < table.size(); ++k) __builtin_memcpy(&vals[k], &table[k], sizeof(B));
-    VEXHIP_TRY(hipMemcpyAsync(values, vals.data(), sizeof(V) * 256, hipMemcpyHostToDevice, s));
-    VEXHIP_TRY(hipStreamSynchronize(s));
-    *nvalues = hinfo[0];
-    return 0;
+    VEXHIP_TRY(d.free_now());
+    return upload_values<V>(s, host.data(), hinfo, values, nvalues);          // too many distinct values: they stay as they are
 }
 
 // deltas[256] / values[256]: device tables as the two separate analyses write them; *ndeltas / *nvalues = -1 when not applicable
@@ -1742,59 +1767,37 @@ int analyze_fused(int dev, void *stream, int64_t n, const P *ptr, const int *col
     hipStream_t s = as_stream(stream);
     // [int set: HASH_SLOTS + 2 info][value set: HASH_SLOTS B + 2 int info][max col]
     const size_t dbytes = sizeof(int) * (HASH_SLOTS + 2), vbytes = sizeof(B) * HASH_SLOTS + 2 * sizeof(int);
-    char *d = nullptr;
+    dev_buf<char> d;
     setup_trace trace(s);
-    VEXHIP_TRY(hipMalloc(&d, dbytes + vbytes + sizeof(int) + 64));
+    VEXHIP_TRY(d.alloc(dbytes + vbytes + sizeof(int) + 64));
     trace.mark("  fused: hipMalloc");
-    int *dset = reinterpret_cast<int *>(d);
-    B *vset = reinterpret_cast<B *>(d + ((dbytes + 15) / 16) * 16);
+    int *dset = reinterpret_cast<int *>(d.p);
+    B *vset = reinterpret_cast<B *>(d.p + ((dbytes + 15) / 16) * 16);
     int *vinfo = reinterpret_cast<int *>(vset + HASH_SLOTS);
     int *dmax = vinfo + 2;
     std::vector<int> hd(HASH_SLOTS + 2, EMPTY);
     hd[HASH_SLOTS] = 0; hd[HASH_SLOTS + 1] = 0;
-    hipError_t e = hipMemcpyAsync(dset, hd.data(), dbytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(vset, 0xff, sizeof(B) * HASH_SLOTS, s);
-    if (e == hipSuccess) e = hipMemsetAsync(vinfo, 0, 2 * sizeof(int), s);
-    if (e == hipSuccess) e = hipMemsetAsync(dmax, 0xff, sizeof(int), s);
+    VEXHIP_TRY(hipMemcpyAsync(dset, hd.data(), dbytes, hipMemcpyHostToDevice, s));
+    VEXHIP_TRY(hipMemsetAsync(vset, 0xff, sizeof(B) * HASH_SLOTS, s));
+    VEXHIP_TRY(hipMemsetAsync(vinfo, 0, 2 * sizeof(int), s));
+    VEXHIP_TRY(hipMemsetAsync(dmax, 0xff, sizeof(int), s));
     std::vector<B> hv(HASH_SLOTS);
     int vi[2] = {0, 0}, hmax = -1;
     trace.mark("  fused: H2D + memsets");
-    if (e == hipSuccess) {
-        analyze_fused_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, val, dset, dset + HASH_SLOTS, vset, vinfo, dmax);
-        e = hipGetLastError();
-    }
+    analyze_fused_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, val, dset, dset + HASH_SLOTS, vset, vinfo, dmax);
+    VEXHIP_LAUNCH_CHECK();
     trace.mark("  fused: kernel");
-    if (e == hipSuccess) e = hipMemcpyAsync(hd.data(), dset, dbytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), vset, sizeof(B) * HASH_SLOTS, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(vi, vinfo, sizeof(vi), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hmax, dmax, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    VEXHIP_TRY(hipMemcpyAsync(hd.data(), dset, dbytes, hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(hv.data(), vset, sizeof(B) * HASH_SLOTS, hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(vi, vinfo, sizeof(vi), hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(&hmax, dmax, sizeof(int), hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipStreamSynchronize(s));
     trace.mark("  fused: D2H");
-    (void)hipFree(d);
+    (void)d.free_now();
     trace.mark("  fused: hipFree");
-    VEXHIP_TRY(e);
     *max_col = hmax;
-    if (!(hd[HASH_SLOTS + 1] != 0 || hd[HASH_SLOTS] > 254 || hd[HASH_SLOTS] < 1)) {
-        std::vector<int> table;
-        for (int k = 0; k < HASH_SLOTS; ++k) if (hd[k] != EMPTY) table.push_back(hd[k]);
-        std::sort(table.begin(), table.end());
-        if ((int)table.size() != hd[HASH_SLOTS]) return fail(__FILE__, __LINE__, "diagonal set is inconsistent");
-        table.resize(256, INT_MAX);
-        VEXHIP_TRY(hipMemcpyAsync(deltas, table.data(), sizeof(int) * 256, hipMemcpyHostToDevice, s));
-        VEXHIP_TRY(hipStreamSynchronize(s));
-        *ndeltas = hd[HASH_SLOTS];
-    }
-    if (*ndeltas > 0 && !(vi[1] != 0 || vi[0] > 255 || vi[0] < 1)) {
-        std::vector<B> table;
-        for (B b : hv) if (b != ~B(0)) table.push_back(b);
-        std::sort(table.begin(), table.end());
-        if ((int)table.size() != vi[0]) return fail(__FILE__, __LINE__, "value set is inconsistent");
-        std::vector<V> vals(256, V(0));
-        for (size_t k = 0; k < table.size(); ++k) __builtin_memcpy(&vals[k], &table[k], sizeof(B));
-        VEXHIP_TRY(hipMemcpyAsync(values, vals.data(), sizeof(V) * 256, hipMemcpyHostToDevice, s));
-        VEXHIP_TRY(hipStreamSynchronize(s));
-        *nvalues = vi[0];
-    }
+    if (int rc = upload_deltas(s, hd.data(), deltas, ndeltas)) return rc;
+    if (*ndeltas > 0) return upload_values<V>(s, hv.data(), vi, values, nvalues);   // value codes only where the diagonals have codes
     return 0;
 }
 
@@ -1806,39 +1809,12 @@ int sell8v_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, 
     if (trav) std::memset(trav, 0, sizeof(*trav));
     if (n == 0) return 0;
     VEXHIP_REQUIRE(ptr && col && val && deltas && values && buf, "NULL argument");
-    VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
-    unsigned long long *dcounts = nullptr;
-    VEXHIP_TRY(hipMalloc(&dcounts, sizeof(unsigned long long) * 256 + 4 * sizeof(int)));
-    int *dinfo = reinterpret_cast<int *>(dcounts + 256);                    // [0] unused, [1] error flag, [2] largest ELL column
-    VEXHIP_TRY(hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * 256 + 2 * sizeof(int), s));
-    if (known_max_col >= 0) {                                               // (the fused analysis of this matrix found it)
-        const int known = (int)known_max_col;
-        VEXHIP_TRY(hipMemcpyAsync(dinfo + 2, &known, sizeof(int), hipMemcpyHostToDevice, s));
-        VEXHIP_TRY(hipStreamSynchronize(s));
-    } else {
-        VEXHIP_TRY(hipMemsetAsync(dinfo + 2, 0xff, sizeof(int), s));
-        ell_max_col_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, dinfo + 2);
-    }
-    if (w <= 8)
-        sell8v_fill_kernel<V, P, true><<<grid_for(dev, ns * (S8_ROWS / 2)), 256, 0, s>>>(n, ns, (int)w, ndeltas, nvalues, ptr, col, val, deltas, values,
-                dinfo + 2, static_cast<char *>(buf), dcounts, dinfo);
-    else
-        sell8v_fill_kernel<V, P, false><<<grid_for(dev, ns * (S8_ROWS / 2)), 256, 0, s>>>(n, ns, (int)w, ndeltas, nvalues, ptr, col, val, deltas, values,
-                dinfo + 2, static_cast<char *>(buf), dcounts, dinfo);
-    std::vector<unsigned long long> counts(256);
-    std::vector<int> table(ndeltas);
-    int hinfo[3] = {0, 0, -1};
-    VEXHIP_TRY(hipMemcpyAsync(counts.data(), dcounts, sizeof(unsigned long long) * 256, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(hinfo, dinfo, sizeof(hinfo), hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(table.data(), deltas, sizeof(int) * ndeltas, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipStreamSynchronize(s));
-    VEXHIP_TRY(hipFree(dcounts));
-    if (max_col) *max_col = hinfo[2];
-    VEXHIP_REQUIRE(hinfo[1] == 0, "SELL8V fill: a diagonal or a value of the matrix is not in its table");
-    if (trav) strip_traversal(n, table, counts, trav);
-    return 0;
+    return coded_fill(dev, s, n, ptr, col, w, deltas, ndeltas, trav, known_max_col, max_col, "SELL8V fill: a diagonal or a value of the matrix is not in its table",
+            [&](auto STAGED, int grid, long long ns, unsigned long long *dcounts, int *dinfo) {
+                sell8v_fill_kernel<V, P, STAGED()><<<grid, 256, 0, s>>>(n, ns, (int)w, ndeltas, nvalues, ptr, col, val, deltas, values, dinfo + 2, static_cast<char *>(buf),
+                        dcounts, dinfo);
+            });
 }
 
 template <typename V>
@@ -1859,15 +1835,17 @@ int spmv_sell8v(int dev, void *stream, int64_t n, V alpha, int append, int64_t w
     if (march && blocks && w <= 8 && g_sell8_variant == 0 && !(tr && tr->order))
         return march_launch<V>(dev, s, n, ns, alpha, append, (int)w, deltas, values, cp, cc, cv, x, y, tr, b, blocks, march, add);
     t8 = attach(t8, add);
-#define PAIRV(W, DICT) sell8_pair_kernel<V, (W <= 8 ? W : 8), true, DICT><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, b, deltas, values, cp, cc, cv, x, y, t8, b, blocks)
-#define CASE(W) case W: if (g_sell8_variant != 1 && W <= 8) { if (blocks) PAIRV(W, true); else PAIRV(W, false); } \
-        else sell8v_kernel<V, W><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, x, y, t8, blocks); break;
-    switch (w) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9)
-        default: sell8v_kernel<V, 0><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, x, y, t8, blocks);
-    }
-#undef CASE
-#undef PAIRV
+    const bool pairs = g_sell8_variant != 1;
+    with_width<9>((int)w, [&](auto W) {
+        if constexpr (W() >= 1 && W() <= 8)                                // (the pair kernel stops at 8 columns; sell8v_kernel is unrolled for 9 as well)
+            if (pairs) {
+                with_bool(blocks != nullptr, [&](auto DICT) {
+                    sell8_pair_kernel<V, W(), true, DICT()><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, b, deltas, values, cp, cc, cv, x, y, t8, b, blocks);
+                });
+                return;
+            }
+        sell8v_kernel<V, W()><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, x, y, t8, blocks);
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -2001,26 +1979,17 @@ int sell8_analyze(int dev, void *stream, int64_t n, const P *ptr, const int32_t 
     if (n <= 0 || w < 1) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    int *d = nullptr;
-    VEXHIP_TRY(hipMalloc(&d, sizeof(int) * (HASH_SLOTS + 2)));
+    dev_buf<int> d;
+    VEXHIP_TRY(d.alloc(HASH_SLOTS + 2));
     std::vector<int> host(HASH_SLOTS + 2, EMPTY);
     host[HASH_SLOTS] = 0; host[HASH_SLOTS + 1] = 0;
-    VEXHIP_TRY(hipMemcpyAsync(d, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, s));
-    delta_collect_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, d, d + HASH_SLOTS);
-    VEXHIP_TRY(hipMemcpyAsync(host.data(), d, sizeof(int) * host.size(), hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipMemcpyAsync(d.p, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, s));
+    delta_collect_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, d.p, d.p + HASH_SLOTS);
+    VEXHIP_TRY(hipMemcpyAsync(host.data(), d.p, sizeof(int) * host.size(), hipMemcpyDeviceToHost, s));
     VEXHIP_TRY(hipStreamSynchronize(s));
-    VEXHIP_TRY(hipFree(d));
+    VEXHIP_TRY(d.free_now());
     if (env(ENV_VEXHIP_DEBUG)) std::fprintf(stderr, "sell8 analyze: count %d overflow %d\n", host[HASH_SLOTS], host[HASH_SLOTS + 1]);
-    if (host[HASH_SLOTS + 1] != 0 || host[HASH_SLOTS] > 254 || host[HASH_SLOTS] < 1) return 0;   // not a banded matrix (codes 254 and 255 are padding)
-    std::vector<int> table;
-    for (int k = 0; k < HASH_SLOTS; ++k) if (host[k] != EMPTY) table.push_back(host[k]);
-    std::sort(table.begin(), table.end());
-    if ((int)table.size() != host[HASH_SLOTS]) return fail(__FILE__, __LINE__, "diagonal set is inconsistent");
-    table.resize(256, INT_MAX);
-    VEXHIP_TRY(hipMemcpyAsync(deltas, table.data(), sizeof(int) * 256, hipMemcpyHostToDevice, s));
-    VEXHIP_TRY(hipStreamSynchronize(s));
-    *ndeltas = host[HASH_SLOTS];
-    return 0;
+    return upload_deltas(s, host.data(), deltas, ndeltas);                    // (more than 254 diagonals: not a banded matrix)
 }
 
 int sell8_apply_halo(int dev, hipStream_t s, long long own_rows, double alpha, int append, int w, bool vcoded, const void *buf, const void *pool,
@@ -2037,21 +2006,21 @@ int sell8v_runs_plan(int dev, void *stream, const void *pool, int64_t nblocks, i
     if (!pool || !deltas || !values || nblocks < 1 || w < 10 || w > 3 * RUNS_GROUPS) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    int *desc = nullptr;
+    dev_buf<int> desc;
     const size_t ints = (size_t)nblocks * 4 * RUNS_STRIDE;
-    VEXHIP_TRY(hipMalloc(reinterpret_cast<void **>(&desc), sizeof(int) * (ints + 2)));
-    int *total = desc + ints;                                                          // {columns in fast groups, columns that hold entries} over all waves of all blocks
-    hipError_t e = hipMemsetAsync(desc, 0, sizeof(int) * (ints + 2), s);
-    if (e == hipSuccess) { sell8v_runs_plan_kernel<V><<<(unsigned)nblocks, 256, 0, s>>>(static_cast<const char *>(pool), (int)w, deltas, values, desc, total); e = hipGetLastError(); }
+    VEXHIP_TRY(desc.alloc(ints + 2));
+    int *total = desc.p + ints;                                                        // {columns in fast groups, columns that hold entries} over all waves of all blocks
+    VEXHIP_TRY(hipMemsetAsync(desc.p, 0, sizeof(int) * (ints + 2), s));
+    sell8v_runs_plan_kernel<V><<<(unsigned)nblocks, 256, 0, s>>>(static_cast<const char *>(pool), (int)w, deltas, values, desc.p, total);
+    VEXHIP_LAUNCH_CHECK();
     int found[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(found, total, sizeof(found), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    VEXHIP_TRY(hipMemcpyAsync(found, total, sizeof(found), hipMemcpyDeviceToHost, s));
+    VEXHIP_TRY(hipStreamSynchronize(s));
     // Worth it where most columns are fast: the codes' path of this kernel takes its columns one at a time (the any-width kernel eight at a
     // time).  A 19-point row -- five triples and four single columns, the triples at columns 1, 5, 8, 11, 15: not aligned -- is slower through
     // it (320^3: 0.478 ms against 0.339) and keeps the any-width kernel; a form with triples at any column and single fast columns (a state
     // per column instead of straight-line groups) lost on BOTH (0.458 and 0.470 ms, profiles/r06_runs_of_three.md).
-    if (e != hipSuccess || found[0] * 4 < found[1] * 3) { (void)hipFree(desc); return e == hipSuccess ? 0 : check(e, __FILE__, __LINE__); }
-    *desc_out = desc;
+    if (found[0] * 4 >= found[1] * 3) *desc_out = desc.release();
     return 0;
 }
 
@@ -2085,27 +2054,24 @@ int csr_traversal(int dev, void *stream, int64_t n, const P *ptr, const int32_t 
     if (n <= 0) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    int *deltas = nullptr;
-    VEXHIP_TRY(hipMalloc(&deltas, sizeof(int) * 256 + sizeof(unsigned long long) * 256));
-    unsigned long long *dcounts = reinterpret_cast<unsigned long long *>(deltas + 256);
+    dev_buf<int> deltas;                                 // [diagonal table: 256 ints][their counts: 256 x 8 bytes]
+    VEXHIP_TRY(deltas.alloc(256 + 256 * sizeof(unsigned long long) / sizeof(int)));
+    unsigned long long *dcounts = reinterpret_cast<unsigned long long *>(deltas.p + 256);
     int nd = -1;
     const int w = 64;                                    // the first 64 entries of every row decide
-    int rc = sell8_analyze<P>(dev, stream, n, ptr, col, w, deltas, &nd);
-    if (rc == 0 && nd > 0) {
+    if (int rc = sell8_analyze<P>(dev, stream, n, ptr, col, w, deltas.p, &nd)) return rc;
+    if (nd > 0) {
         std::vector<unsigned long long> counts(256);
         std::vector<int> table(nd);
-        hipError_t e = hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * 256, s);
-        if (e == hipSuccess) {
-            csr_delta_count_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, w, nd, ptr, col, deltas, dcounts);
-            e = hipMemcpyAsync(counts.data(), dcounts, sizeof(unsigned long long) * 256, hipMemcpyDeviceToHost, s);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(table.data(), deltas, sizeof(int) * nd, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { (void)hipFree(deltas); return check(e, __FILE__, __LINE__); }
+        VEXHIP_TRY(hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * 256, s));
+        csr_delta_count_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, w, nd, ptr, col, deltas.p, dcounts);
+        VEXHIP_TRY(hipMemcpyAsync(counts.data(), dcounts, sizeof(unsigned long long) * 256, hipMemcpyDeviceToHost, s));
+        VEXHIP_TRY(hipMemcpyAsync(table.data(), deltas.p, sizeof(int) * nd, hipMemcpyDeviceToHost, s));
+        VEXHIP_TRY(hipStreamSynchronize(s));
         strip_traversal(n, table, counts, traversal, rows_per_block);
     }
-    VEXHIP_TRY(hipFree(deltas));
-    return rc;
+    VEXHIP_TRY(deltas.free_now());
+    return 0;
 }
 
 // the combinations in use (64-bit row pointers: a device may hold 2^31 entries or more; columns stay 32-bit)

@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "traversal.hpp"
 #include "storage.hpp"
+#include "dispatch.hpp"
 
 namespace vexhip {
 namespace {
@@ -293,20 +294,11 @@ void launch(hipStream_t s, long long grid, long long n, long long ns, V alpha, i
         const int *deltas, const V *values, const int *cp, const int *cc, const V *cv, const rhs_set<V> &io, const trav_dev &t,
         const char *pool, const int *blocks)
 {
-#define LAUNCH(W)                                                                                              \
-    do {                                                                                                       \
-        if constexpr (CODES == 2) spmm_sell8v_kernel<V, W, NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, values, cp, cc, cv, io, t, blocks); \
-        else if constexpr (CODES == 1) spmm_sell8_kernel<V, W, NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, cp, cc, cv, io, t, pool, blocks); \
-        else spmm_sell_kernel<V, W, NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, cp, cc, cv, io, t);               \
-    } while (0)
-    switch (w) {          // unrolled for the usual stencil widths (1-D, 2-D 5/9-point, 3-D 7-point); any other width loops
-        case 3: LAUNCH(3); break;
-        case 5: LAUNCH(5); break;
-        case 7: LAUNCH(7); break;
-        case 9: LAUNCH(9); break;
-        default: LAUNCH(0);
-    }
-#undef LAUNCH
+    with_width_of<3, 5, 7, 9>(w, [&](auto W) {    // unrolled for the usual stencil widths (1-D, 2-D 5/9-point, 3-D 7-point); any other width loops
+        if constexpr (CODES == 2) spmm_sell8v_kernel<V, W(), NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, values, cp, cc, cv, io, t, blocks);
+        else if constexpr (CODES == 1) spmm_sell8_kernel<V, W(), NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, cp, cc, cv, io, t, pool, blocks);
+        else spmm_sell_kernel<V, W(), NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, cp, cc, cv, io, t);
+    });
 }
 
 } // namespace

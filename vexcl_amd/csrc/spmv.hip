@@ -16,6 +16,7 @@
 #include "traversal.hpp"
 #include "pairing.hpp"
 #include "storage.hpp"
+#include "dispatch.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -582,22 +583,6 @@ int spmv_csr_rows(int dev, void *stream, int64_t nr, V alpha, const int *rows, c
     return 0;
 }
 
-template <typename V, int RPT, bool NT, bool SWZ>
-int launch_hell_w(hipStream_t s, long long grid, long long nb, int64_t n, V alpha, int append,
-        int w, int64_t pitch, const int *ec, const V *ev,
-        const int *cp, const int *cc, const V *cv, const V *x, V *y, trav_dev order)
-{
-#define CASE(W) case W: hell_kernel<V, RPT, W, NT, SWZ><<<(unsigned)grid, 256, 0, s>>>( \
-        n, nb, alpha, append, w, pitch, ec, ev, cp, cc, cv, x, y, order); break;
-    switch (w) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-        default: hell_kernel<V, RPT, 0, NT, SWZ><<<(unsigned)grid, 256, 0, s>>>(
-                n, nb, alpha, append, w, pitch, ec, ev, cp, cc, cv, x, y, order);
-    }
-#undef CASE
-    return 0;
-}
-
 template <typename V>
 int spmv_hell(int dev, void *stream, int64_t n, V alpha, int append,
         int64_t w, int64_t pitch, const int *ec, const V *ev,
@@ -630,27 +615,28 @@ int spmv_hell(int dev, void *stream, int64_t n, V alpha, int append,
     if (rpt > 1 && w > 0 && ((pitch % 16) != 0 || !aligned16(ec) || !aligned16(ev))) rpt = 1;
     if (rpt == 3 || rpt > 4) rpt = 4;
 
-    trav_dev order = {nullptr, 0, 0, 0};
     const bool ordered = tr && tr->grid_blocks > 0;
     if (ordered) {
         // the traversal was built for kHellOrderRows rows per workgroup
         VEXHIP_REQUIRE(w > 0 && (pitch % 16) == 0 && aligned16(ec) && aligned16(ev), "ordered HELL product needs aligned ELL arrays");
         rpt = kHellOrderRows / 256;
         nt = true;
-        order = trav_dev{tr->order, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
     }
 
     long long nb = (n + (long long)256 * rpt - 1) / ((long long)256 * rpt);
-    long long grid = ordered ? tr->grid_blocks : (swz ? ((nb + 7) / 8) * 8 : nb);
+    long long grid = 0;
+    const trav_dev order = make_traversal(tr, nb, &grid);
+    if (!ordered) grid = swz ? ((nb + 7) / 8) * 8 : nb;
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
 
-#define GO(RPT, NT, SWZ) launch_hell_w<V, RPT, NT, SWZ>(s, grid, nb, n, alpha, append, (int)w, pitch, ec, ev, cp, cc, cv, x, y, order)
-#define GO_RPT(RPT) do { \
-        if (nt) { if (swz) GO(RPT, true, true); else GO(RPT, true, false); } \
-        else    { if (swz) GO(RPT, false, true); else GO(RPT, false, false); } } while (0)
-    if (rpt == 1) GO_RPT(1); else if (rpt == 2) GO_RPT(2); else GO_RPT(4);
-#undef GO_RPT
-#undef GO
+    auto go = [&](auto RPT) {
+        with_bools(nt, swz, [&](auto NT, auto SWZ) {
+            with_width<8>((int)w, [&](auto W) {
+                hell_kernel<V, RPT(), W(), NT(), SWZ()><<<(unsigned)grid, 256, 0, s>>>(n, nb, alpha, append, (int)w, pitch, ec, ev, cp, cc, cv, x, y, order);
+            });
+        });
+    };
+    if (rpt == 1) go(std::integral_constant<int, 1>()); else if (rpt == 2) go(std::integral_constant<int, 2>()); else go(std::integral_constant<int, 4>());
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -691,21 +677,18 @@ int spmv_sell(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
     long long ns = (n + SELL_ROWS - 1) / SELL_ROWS;
-    const bool ordered = tr && tr->grid_blocks > 0;
-    long long grid = ordered ? tr->grid_blocks : ns;
-    trav_dev order = {nullptr, 0, 0, 0};
-    if (ordered) order = trav_dev{tr->order, (int)tr->chunk, (int)tr->planes, (int)tr->plane_blocks};
-    order = attach(order, add);                                    // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
+    long long grid = 0;
+    const trav_dev order = attach(make_traversal(tr, ns, &grid), add);   // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-#define CASE(W) case W: if (g_sell8_variant == 0) sell_pair_kernel<V, W><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, sc, cp, cc, cv, x, y, order); \
-        else sell_kernel<V, W, true><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, sc, cp, cc, cv, x, y, order); break;
-    switch (w) {
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-        default:
+    with_width<8>((int)w, [&](auto W) {
+        if constexpr (W() != 0) {
+            if (g_sell8_variant == 0) sell_pair_kernel<V, W()><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, sc, cp, cc, cv, x, y, order);
+            else sell_kernel<V, W(), true><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, sc, cp, cc, cv, x, y, order);
+        } else {
             if (env(ENV_VEXHIP_SELL_XLOAD)) sell_kernel<V, 0, true, true><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, sc, cp, cc, cv, x, y, order);
             else sell_kernel<V, 0, true><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, (int)w, sc, cp, cc, cv, x, y, order);
-    }
-#undef CASE
+        }
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -717,18 +700,15 @@ int sell_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, co
     VEXHIP_SET_DEVICE(dev);
     long long ns = (n + SELL_ROWS - 1) / SELL_ROWS;
     int grid = (int)std::min<int64_t>((ns * (SELL_ROWS / 2) + 255) / 256, (int64_t)info(dev).cus * 16);
-    int *max_col = nullptr;                                   // largest column of the ELL part (bounds the 16-byte gathers)
-    VEXHIP_TRY(hipMalloc(&max_col, sizeof(int)));
-    hipError_t e = hipMemsetAsync(max_col, 0xff, sizeof(int), as_stream(stream));
-    if (e == hipSuccess) {
-        ell_max_col_kernel<P><<<std::max(1, (int)std::min<int64_t>((n + 255) / 256, (int64_t)info(dev).cus * 16)), 256, 0, as_stream(stream)>>>(
-                n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, max_col);
-        sell_fill_kernel<V, P><<<std::max(1, grid), 256, 0, as_stream(stream)>>>(n, ns, (int)w, ptr, col, val, max_col, static_cast<char *>(sell));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(max_col);
-    return check(e, __FILE__, __LINE__);
+    dev_buf<int> max_col;                                     // largest column of the ELL part (bounds the 16-byte gathers)
+    VEXHIP_TRY(max_col.alloc(1));
+    VEXHIP_TRY(hipMemsetAsync(max_col.p, 0xff, sizeof(int), as_stream(stream)));
+    ell_max_col_kernel<P><<<std::max(1, (int)std::min<int64_t>((n + 255) / 256, (int64_t)info(dev).cus * 16)), 256, 0, as_stream(stream)>>>(
+            n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, max_col.p);
+    sell_fill_kernel<V, P><<<std::max(1, grid), 256, 0, as_stream(stream)>>>(n, ns, (int)w, ptr, col, val, max_col.p, static_cast<char *>(sell));
+    VEXHIP_LAUNCH_CHECK();
+    VEXHIP_TRY(hipStreamSynchronize(as_stream(stream)));
+    return 0;
 }
 
 template <typename V, typename I>
@@ -754,15 +734,12 @@ int spmv_csr(int dev, void *stream, int64_t n, V alpha, int append,
     if (tr && tr->grid_blocks > 0) order = make_traversal(tr, nb, &grid);
     order = attach(order, add);                                    // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*)
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
-#define LAUNCH(NT, SWZ) csr_stream_kernel<V, I, NT, SWZ><<<(unsigned)grid, CSR_BLOCK, 0, s>>>( \
-        n, nb, alpha, append, ptr, col, val, x, y, order)
-    if (!(variant & 4)) {             // second form (default)
-        if (swz) csr_stream2_kernel<V, I, true, 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
-        else csr_stream2_kernel<V, I, false, 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
-    }
-    else if (nt) { if (swz) LAUNCH(true, true); else LAUNCH(true, false); }
-    else    { if (swz) LAUNCH(false, true); else LAUNCH(false, false); }
-#undef LAUNCH
+    with_bools(nt, swz, [&](auto NT, auto SWZ) {
+        if (!(variant & 4))           // second form (default)
+            csr_stream2_kernel<V, I, SWZ(), 2048><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
+        else
+            csr_stream_kernel<V, I, NT(), SWZ()><<<(unsigned)grid, CSR_BLOCK, 0, s>>>(n, nb, alpha, append, ptr, col, val, x, y, order);
+    });
     VEXHIP_LAUNCH_CHECK();
     return 0;
 }
