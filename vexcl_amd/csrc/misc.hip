@@ -149,6 +149,20 @@ void width_hist_kernel(long long n, const P *__restrict__ ptr, int cap, unsigned
     if (s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)s_h[threadIdx.x]);
 }
 
+// the widths of the rows in the cap bucket (width >= cap), in any order; out holds as many ints as the bucket counted
+template <typename P>
+__global__ __launch_bounds__(256)
+void wide_rows_kernel(long long n, const P *__restrict__ ptr, int cap, long long capacity, int *out, unsigned long long *count) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x) {
+        int w = (int)(ptr[i + 1] - ptr[i]);
+        if (w >= cap) {
+            const unsigned long long at = atomicAdd(count, 1ull);
+            if ((long long)at < capacity) out[at] = w;
+        }
+    }
+}
+
 template <typename P>
 __global__ __launch_bounds__(256)
 void tail_count_kernel(long long n, const P *__restrict__ ptr, int w, int *cnt, unsigned long long *total) {
@@ -261,10 +275,35 @@ int hell_analyze(int dev, void *stream, int64_t n, const P *ptr,
     int64_t maxw = (int64_t)(int)(h[0] & 0xffffffffu);
     // hybrid_ell.inl:103-110: smallest i with 3 * (#rows wider than i) < n
     const double ell_vs_csr = 3.0;
+    // The histogram is exact below cap only: bucket cap holds every row of cap entries or more.
     int64_t w = maxw, rows = n;
-    for (int64_t i = 0; i < maxw && i <= cap; ++i) {
+    bool found = false;
+    for (int64_t i = 0; i < maxw && i < cap; ++i) {
         rows -= (int64_t)h[2 + i];
-        if (ell_vs_csr * (double)rows < (double)n) { w = i; break; }
+        if (ell_vs_csr * (double)rows < (double)n) { w = i; found = true; break; }
+    }
+    if (!found && maxw > cap) {
+        // A third of the rows or more hold cap entries or more (`rows` of them: at most nnz / cap).  Their widths are sorted on the host; the
+        // count of wider rows changes only at a width some row has, so the candidates are those widths, in ascending order.  The last
+        // one is maxw, with no wider row: the loop always ends there at the latest, as the reference's does.
+        const int64_t wide = rows;
+        int *dw = nullptr;
+        VEXHIP_TRY(hipMalloc(&dw, sizeof(int) * (size_t)wide));
+        wide_rows_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, ptr, cap, wide, dw, d + 1);
+        std::vector<int> ws((size_t)wide);
+        unsigned long long counted = 0;
+        VEXHIP_TRY(hipMemcpyAsync(ws.data(), dw, sizeof(int) * (size_t)wide, hipMemcpyDeviceToHost, s));
+        VEXHIP_TRY(hipMemcpyAsync(&counted, d + 1, sizeof(counted), hipMemcpyDeviceToHost, s));
+        VEXHIP_TRY(hipMemsetAsync(d + 1, 0, sizeof(unsigned long long), s));      // the tail total below starts from 0
+        VEXHIP_TRY(hipStreamSynchronize(s));
+        VEXHIP_TRY(hipFree(dw));
+        if ((int64_t)counted != wide) { (void)hipFree(d); VEXHIP_REQUIRE(false, "row widths changed during the analysis"); }
+        std::sort(ws.begin(), ws.end());
+        for (size_t k = 0; k < ws.size();) {
+            size_t e = k; while (e < ws.size() && ws[e] == ws[k]) ++e;
+            if (ell_vs_csr * (double)(ws.size() - e) < (double)n) { w = ws[k]; break; }
+            k = e;
+        }
     }
     if (w < maxw) {
         tail_count_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, ptr, (int)w, nullptr, d + 1);
