@@ -3,12 +3,13 @@
 device buffers.
 
 What runs where
-  * test_analyses_*: `vexhip_sell8_analyze_i32`, `vexhip_sell8v_analyze_f64_i32` / `_f32_i32` (`delta_collect_kernel`,
-    `value_collect_kernel`, `upload_table`) against `tables()`; the limits 254 / 255 diagonals and 255 / 256 values with every row
+  * test_analyses_*: `vexhip_sell8_analyze_i32`, `vexhip_sell8v_analyze_f64_i32` / `_f32_i32` (`collect_kernel<diagonal_keys>`,
+    `collect_kernel<value_keys<V>>`, `upload_table`) against `tables()`; the limits 254 / 255 diagonals and 255 / 256 values with every row
     holding all of them (the per-workgroup check decides) and spread over the rows (only the merged set decides), more than 1024
-    diagonals, the value whose bits are all ones, a matrix without entries; `analyze_fused_kernel` through `vexhip_spmat_create_*`.
-  * test_fills_*: `vexhip_sell8_fill_*` / `vexhip_sell8v_fill_*` (`sell8_fill_kernel`, `sell8v_fill_kernel`, staged and not,
-    `ell_max_col_kernel`) for the ELL widths 1..9 and 12 on every family of matrices below, byte for byte against `encode_sell8` /
+    diagonals, the value whose bits are all ones, a matrix without entries; `analyze_fused_kernel`, which shares their `collector`,
+    through `vexhip_spmat_create_*` on ordinary matrices and at the same limits.
+  * test_fills_*: `vexhip_sell8_fill_*` / `vexhip_sell8v_fill_*` (`coded_fill_kernel` over the storage policies
+    `stored_values<V>` / `coded_values<V>`, staged and not, `ell_max_col_kernel`) for the ELL widths 1..9 and 12 on every family of matrices below, byte for byte against `encode_sell8` /
     `encode_sell8v`; `vexhip_slice_dictionary` on the filled buffers.
   * test_products_streamed_*: `vexhip_spmv_sell8_*` and `vexhip_spmv_sell8v_*` under the variant words 0 and 1:
     `sell8_pair_kernel<W, VCODED, false>` (widths 1..8, word 0), `sell8_kernel<W>` and `sell8v_kernel<W>` (word 1; `sell8v_kernel<9>`
@@ -1014,40 +1015,78 @@ def fused_matrices(oracle):
             (ptr, col, oracle.random_f64(77, len(col)) - 0.5, "sell32")]
 
 
+def fused_limit_matrices(oracle, dtype):
+    """(name, ptr, col, values of `dtype`, the row length the hybrid-ELL width must cover): the matrices of `test_analyses_limits`
+    as whole matrices -- 254 / 255 diagonals over three values; 255 / 256 values, spread over one diagonal, all of them in every
+    row (which then holds as many diagonals: neither is coded), and all of them in every two rows of 128 diagonals (a workgroup
+    sees them all and the diagonals stay coded); the value whose bits are all ones."""
+    out = []
+    for count in (254, 255):
+        for spread in (False, True):
+            ptr, col, _ = limit_diagonals(oracle, count, spread)
+            out.append(("%d diagonals%s" % (count, ", spread" if spread else ""), ptr, col, ((col % 3 + 1) / 4.0).astype(dtype), 1 if spread else count))
+    for count in (255, 256):
+        for spread in (False, True):
+            ptr, val, _ = limit_values(count, spread, dtype)
+            rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+            col = (rows + np.arange(len(val)) - ptr[:-1][rows]).astype(np.int32)               # entry k of row r: column r + k
+            out.append(("%d values%s" % (count, ", spread" if spread else ""), ptr, col, val, 1 if spread else count))
+        pool = ((np.arange(count) + 1) / 512.0).astype(dtype)
+        k = np.arange(300 * 128, dtype=np.int64)
+        out.append(("%d values, in every two rows" % count, np.arange(301, dtype=np.int32) * 128, (k // 128 + k % 128).astype(np.int32), pool[k % count], 128))
+    val = ((np.arange(10) + 1) / 8.0).astype(dtype)
+    val.view(BITS[dtype])[3] = ~BITS[dtype](0)
+    out.append(("all-ones value", np.arange(11, dtype=np.int32), np.arange(10, dtype=np.int32), val, 1))
+    return out
+
+
+def check_fused(G, oracle, ptr, col, val, storage=None, row_length=None):
+    """One matrix through vexhip_spmat_create_*: what its fused analysis left in the handle against the separate analyses at
+    info.ell_width.  storage: the storage it must choose, where the case names one."""
+    from vexcl_amd import _capi
+    L, dtype = G.L, val.dtype.type
+    assert row_length is None or oracle.hell_width(ptr) >= row_length, (oracle.hell_width(ptr), row_length)
+    dp, dc, dv = device_csr(G, ptr, col, val)
+    h = ctypes.c_void_p()
+    getattr(L, "spmat_create_%s_i32" % _sfx(dtype))(0, G.stream(), len(ptr) - 1, _vp(dp), _vp(dc), _vp(dv), _capi.SPMAT_AUTO, 0, ctypes.byref(h))
+    try:
+        info = _capi.SpMatInfo()
+        L.spmat_get_info(h, ctypes.byref(info))
+        w = int(info.ell_width)
+        assert w == oracle.hell_width(ptr) and (storage is None or _capi.SPMAT_NAMES[info.format] == storage), (storage, info.format, w)
+        nd, table = analyze_diagonals(G, ptr, col, w)
+        nv, vtable = analyze_values(G, ptr, val, w)
+        if not (nd > 0 and nv > 0):
+            nv = -1                                                # (value codes only where the diagonals have codes and the values fit)
+        assert (info.ndeltas, info.nvalues) == (nd, nv), (storage, info.ndeltas, nd, info.nvalues, nv)
+        assert bool(info.deltas) == (nd > 0) and bool(info.values) == (nv > 0)
+        assert storage is None or (nd > 0, nv > 0) == (storage != "sell32", storage == "sell8v"), (storage, nd, nv)
+        if nd > 0:
+            got = np.empty(256, dtype=np.int32)
+            L.memcpy_d2h(0, got.ctypes.data, info.deltas, got.nbytes, G.stream(), 1)
+            assert np.array_equal(got, table), storage
+        if nv > 0:
+            got = np.empty(256, dtype=BITS[dtype])
+            L.memcpy_d2h(0, got.ctypes.data, info.values, got.nbytes, G.stream(), 1)
+            assert np.array_equal(got, vtable), storage
+        return nd, nv
+    finally:
+        L.spmat_destroy(h)
+
+
 @gpu
 @every_dtype
 def test_fused_analysis_reports_what_the_separate_analyses_do(G, oracle, dtype):
     """`analyze_fused_kernel` (vexhip_spmat_create_*): ndeltas, nvalues and both tables as `vexhip_sell8_analyze_i32` and
     `vexhip_sell8v_analyze_*` give them at info.ell_width, for a value-coded matrix, one with stored values and one with 32-bit
-    columns."""
-    from vexcl_amd import _capi
-    L = G.L
+    columns -- and at the limits of both sets (fused_limit_matrices), where the verdicts are known as well."""
     for ptr, col, val64, storage in fused_matrices(oracle):
-        val = val64.astype(dtype)
-        dp, dc, dv = device_csr(G, ptr, col, val)
-        h = ctypes.c_void_p()
-        getattr(L, "spmat_create_%s_i32" % _sfx(dtype))(0, G.stream(), len(ptr) - 1, _vp(dp), _vp(dc), _vp(dv), _capi.SPMAT_AUTO, 0, ctypes.byref(h))
-        try:
-            info = _capi.SpMatInfo()
-            L.spmat_get_info(h, ctypes.byref(info))
-            w = int(info.ell_width)
-            assert _capi.SPMAT_NAMES[info.format] == storage and w == oracle.hell_width(ptr), (storage, info.format, w)
-            nd, table = analyze_diagonals(G, ptr, col, w)
-            nv, vtable = analyze_values(G, ptr, val, w)
-            if storage != "sell8v":
-                nv = -1                                                # (value codes only where the diagonals have codes and the values fit)
-            assert (info.ndeltas, info.nvalues) == (nd, nv), (storage, info.ndeltas, nd, info.nvalues, nv)
-            assert (nd > 0) == (storage != "sell32") and bool(info.deltas) == (nd > 0) and bool(info.values) == (nv > 0)
-            if nd > 0:
-                got = np.empty(256, dtype=np.int32)
-                L.memcpy_d2h(0, got.ctypes.data, info.deltas, got.nbytes, G.stream(), 1)
-                assert np.array_equal(got, table), storage
-            if nv > 0:
-                got = np.empty(256, dtype=BITS[dtype])
-                L.memcpy_d2h(0, got.ctypes.data, info.values, got.nbytes, G.stream(), 1)
-                assert np.array_equal(got, vtable), storage
-        finally:
-            L.spmat_destroy(h)
+        check_fused(G, oracle, ptr, col, val64.astype(dtype), storage)
+    verdicts = {name: check_fused(G, oracle, ptr, col, val, None, row_length) for name, ptr, col, val, row_length in fused_limit_matrices(oracle, dtype)}
+    assert verdicts == {"254 diagonals": (254, 3), "254 diagonals, spread": (254, 3), "255 diagonals": (-1, -1), "255 diagonals, spread": (-1, -1),
+                        "255 values": (-1, -1), "255 values, spread": (1, 255), "255 values, in every two rows": (128, 255),
+                        "256 values": (-1, -1), "256 values, spread": (1, -1), "256 values, in every two rows": (128, -1),
+                        "all-ones value": (1, -1)}, verdicts
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1425,6 +1464,12 @@ def test_generators_encoders_and_host_models(oracle):
         w = oracle.hell_width(ptr)
         deltas, values, _ = tables(ptr, col, val, w)
         assert (len(deltas) <= 254, len(values) <= 255) == {"sell8v": (True, True), "sell8": (True, False), "sell32": (False, False)}[storage]
+    for dtype in DTYPES:
+        for name, ptr, col, val, row_length in fused_limit_matrices(oracle, dtype):
+            w = oracle.hell_width(ptr)
+            deltas, values, _ = tables(ptr, col, val, w)
+            assert w == row_length == np.diff(ptr).max() and val.dtype == dtype and len(col) == len(val) == ptr[-1], name
+            assert "%d diagonals" % len(deltas) in name or "%d values" % len(values) in name or "all-ones" in name, (name, len(deltas), len(values))
 
     # launch geometry
     for nb in (1, 2, 4, 13):

@@ -43,12 +43,11 @@ thread_local int64_t g_fill_max_col = -1;
 namespace {
 
 constexpr int S8_ROWS = 512;
-constexpr int S8_PAD = 255;              // padding (254 = padding too, see the pair kernels)
-constexpr unsigned S8_FIRST_PAD = 254;
-constexpr unsigned S8_PAD_UNSAFE = 254;     // padding whose partner must not use the 16-byte load (pair kernels)
+constexpr unsigned S8_PAD_UNSAFE = 254;            // padding whose partner must not use the 16-byte load (pair kernels)
+constexpr unsigned S8_PAD = 255;                   // padding
+constexpr unsigned S8_FIRST_PAD = S8_PAD_UNSAFE;   // codes from here on are padding: a table holds at most 254 diagonals
 constexpr int HASH_SLOTS = 1024;
 constexpr int LOCAL_SLOTS = 512;          // per-workgroup set: twice the 255 entries a table may hold
-constexpr int EMPTY = INT_MIN;
 
 typedef double double2v __attribute__((ext_vector_type(2)));
 typedef float  float2v  __attribute__((ext_vector_type(2)));
@@ -60,6 +59,9 @@ __host__ __device__ inline long long slice_bytes(long long w, long long value_by
 template <typename V> struct vec2;
 template <> struct vec2<double> { typedef double2v type; };
 template <> struct vec2<float> { typedef float2v type; };
+template <typename V> struct bits_of;
+template <> struct bits_of<double> { typedef unsigned long long type; };
+template <> struct bits_of<float> { typedef unsigned type; };
 
 // ---------------------------------------------------------------------------
 template <typename V, int W>
@@ -128,64 +130,212 @@ void sell8_kernel(long long n, long long nslices, V alpha, int append, int ell_w
     store_pair<V>(n, i, alpha, append, sum, y, trav);
 }
 
-// ---- set-up: which diagonals does the ELL part use? ------------------------------------
-__device__ __forceinline__ bool set_insert(int *set, int slots, int d, bool *is_new) {
-    unsigned h = ((unsigned)d * 2654435761u) % (unsigned)slots;
+// ---- set-up: which diagonals and which values does the ELL part use? --------------------
+// The sets are open-addressing hash sets of diagonals (int) or of value bit patterns (unsigned, unsigned long long).  What a
+// key type brings: the marker of an empty slot and the hash (slot placement is invisible to the host, probe lengths are not
+// invisible to the clock: each set keeps the hash it was measured with).
+template <typename K> struct set_key {                                     // value bits: all-ones = empty
+    static constexpr K empty = ~K(0);
+    static __device__ __forceinline__ unsigned hash(K v) { return (unsigned)((unsigned long long)v * 0x9E3779B97F4A7C15ull >> 40); }
+};
+template <> struct set_key<int> {                                          // diagonals: INT_MIN = empty
+    static constexpr int empty = INT_MIN;
+    static __device__ __forceinline__ unsigned hash(int d) { return (unsigned)d * 2654435761u; }
+};
+
+template <typename K>
+__device__ __forceinline__ bool set_insert(K *set, int slots, K key, bool &is_new) {
+    unsigned h = set_key<K>::hash(key) % (unsigned)slots;
     for (int probe = 0; probe < slots; ++probe) {
-        int old = atomicCAS(&set[h], EMPTY, d);
-        if (old == EMPTY) { if (is_new) *is_new = true; return true; }
-        if (old == d) return true;
+        const K old = atomicCAS(&set[h], set_key<K>::empty, key);
+        if (old == set_key<K>::empty) { is_new = true; return true; }
+        if (old == key) return true;
         h = (h + 1) % (unsigned)slots;
     }
     return false;
 }
 
-// gset: HASH_SLOTS ints (EMPTY-filled); info[0] = number of distinct diagonals, info[1] = overflow flag
-template <typename P>
+// What the sets collect: the key of an entry of `row`, false where it has none (such a matrix has no table: overflow), and
+// the most keys a table holds.
+struct diagonal_keys {
+    typedef int elem;                                                      // read from col
+    typedef int key;
+    static constexpr int limit = 254;                                      // codes 254 and 255 are padding
+    static __device__ __forceinline__ bool key_of(int c, long long row, int &d) {
+        const long long dl = (long long)c - row;
+        if (dl <= INT_MIN || dl > INT_MAX) return false;
+        d = (int)dl;
+        return true;
+    }
+};
+template <typename V> struct value_keys {
+    typedef V elem;                                                        // read from val
+    typedef typename bits_of<V>::type key;
+    static constexpr int limit = 255;
+    static __device__ __forceinline__ bool key_of(V v, long long, key &bits) {
+        __builtin_memcpy(&bits, &v, sizeof(key));
+        return bits != ~key(0);                                            // the one pattern that cannot be stored (a NaN payload)
+    }
+};
+
+// The set of one workgroup (the kernel's LDS: the slots, an overflow flag, a count) on its way into the global one.
+// gset: HASH_SLOTS keys (empty-filled); info[0] = number of distinct keys in gset, info[1] = overflow flag.
+//   A matrix without structure, or one whose values are all different, fills a set at once, and a full set costs a whole
+// probe sequence per insertion.  So: stop at the first key beyond LIMIT (a half-full table: short probe sequences), tell the
+// other workgroups through the global flag -- `over` starts from it, so later workgroups do not even begin -- and do not
+// merge.  With the first version of this (probe until the 512-slot table is FULL, flag raised only at the end) the value
+// analysis of the 512^3 variable-coefficient matrix took 143 ms (profiles/r02_*cpp_kernel_stats.csv).
+template <typename K, int LIMIT>
+struct collector {
+    K (&set)[LOCAL_SLOTS];                                                 // the kernel's LDS
+    int &over, &count;
+    __device__ __forceinline__ void init(const int *info) {               // every thread; a barrier follows
+        for (int k = threadIdx.x; k < LOCAL_SLOTS; k += blockDim.x) set[k] = set_key<K>::empty;
+        if (threadIdx.x == 0) { over = *(const volatile int *)&info[1]; count = 0; }
+    }
+    __device__ __forceinline__ bool stopped(const int *info) const { return *(const volatile int *)&over || *(const volatile int *)&info[1]; }
+    __device__ __forceinline__ void add(K key, int *info) {
+        bool fresh = false;
+        if (!set_insert(set, LOCAL_SLOTS, key, fresh)) over = 1;
+        else if (fresh && atomicAdd(&count, 1) >= LIMIT) { over = 1; atomicExch(&info[1], 1); }   // one key too many: not coded
+    }
+    __device__ __forceinline__ void merge(K *gset, int *info) const {     // every thread; after a barrier
+        if (over) { if (threadIdx.x == 0) atomicExch(&info[1], 1); return; }
+        for (int k = threadIdx.x; k < LOCAL_SLOTS; k += blockDim.x) {
+            if (set[k] == set_key<K>::empty) continue;
+            bool is_new = false;
+            if (!set_insert(gset, HASH_SLOTS, set[k], is_new)) atomicExch(&info[1], 1);
+            else if (is_new) atomicAdd(&info[0], 1);
+        }
+    }
+};
+
+// The distinct keys of the first w entries of every row: S = diagonal_keys over col, value_keys<V> over val.
+template <class S, typename P>
 __global__ __launch_bounds__(256)
-void delta_collect_kernel(long long n, int w, const P *__restrict__ ptr, const int *__restrict__ col,
-        int *gset, int *info)
+void collect_kernel(long long n, int w, const P *__restrict__ ptr, const typename S::elem *__restrict__ data,
+        typename S::key *gset, int *info)
 {
-    __shared__ int s_set[LOCAL_SLOTS];
+    typedef typename S::key K;
+    __shared__ K s_set[LOCAL_SLOTS];
     __shared__ int s_over, s_count;
-    for (int k = threadIdx.x; k < LOCAL_SLOTS; k += blockDim.x) s_set[k] = EMPTY;
-    if (threadIdx.x == 0) { s_over = *(volatile int *)&info[1]; s_count = 0; }
+    collector<K, S::limit> c{s_set, s_over, s_count};
+    c.init(info);
     __syncthreads();
-    // a matrix without structure overflows the set at once: stop looking (a full set costs a whole probe
-    // sequence per insertion) -- s_over starts from the global flag, so later workgroups do not even begin
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        if (*(volatile int *)&s_over || *(volatile int *)&info[1]) break;
+        if (c.stopped(info)) break;
         const P b = ptr[i], e = ptr[i + 1];
-        int last = EMPTY;
+        K last = set_key<K>::empty;
         for (int j = 0; j < w && b + j < e; ++j) {
-            long long dl = (long long)col[b + j] - i;
-            if (dl <= INT_MIN || dl > INT_MAX) { s_over = 1; continue; }
-            int d = (int)dl;
-            if (d == last) continue;
-            last = d;
-            bool fresh = false;
-            if (!set_insert(s_set, LOCAL_SLOTS, d, &fresh)) s_over = 1;
-            else if (fresh && atomicAdd(&s_count, 1) >= 254) { s_over = 1; atomicExch(&info[1], 1); }   // a 255th diagonal: not coded
+            K key;
+            if (!S::key_of(data[b + j], i, key)) { c.over = 1; continue; }
+            if (key == last) continue;
+            last = key;
+            c.add(key, info);
         }
     }
     __syncthreads();
-    if (s_over) { if (threadIdx.x == 0) atomicExch(&info[1], 1); return; }
-    for (int k = threadIdx.x; k < LOCAL_SLOTS; k += blockDim.x) {
-        if (s_set[k] == EMPTY) continue;
-        bool is_new = false;
-        if (!set_insert(gset, HASH_SLOTS, s_set[k], &is_new)) atomicExch(&info[1], 1);
-        else if (is_new) atomicAdd(&info[0], 1);
-    }
-    if (threadIdx.x == 0 && s_over) atomicExch(&info[1], 1);
+    c.merge(gset, info);
 }
 
-// code of a diagonal (binary search in the sorted table), S8_PAD if it is not there
+// One entry of the fused pass below.  A lane of a structured matrix meets the same key at the same place of every row: what
+// it has inserted once it does not insert again (both sets only grow) -- 64 lanes inserting the same 7 diagonals per row were
+// 64-way conflicts on the LDS set: the kernel was bound by them, not by its loads.  seen[j]: what this lane inserted last at
+// entry position j.
+template <class S, class C, typename K>
+__device__ __forceinline__ void add_once(C &c, int *info, typename S::elem x, long long row, int j, K &last, K (&seen)[8]) {
+    K key;
+    if (!S::key_of(x, row, key)) c.over = 1;
+    else if (key != last && !(j < 8 && key == seen[j])) {
+        last = key;
+        if (j < 8) seen[j] = key;
+        c.add(key, info);
+    }
+}
+
+// Diagonals, values and the largest column of the ELL part in ONE pass over the CSR arrays (round 3: two collect_kernel passes
+// + ell_max_col read ptr / col / val three times, 12 ms of the 512^3 set-up).  Same sets, same overflow rules as
+// collect_kernel.  A workgroup takes 256 consecutive rows at a time; their entries are one contiguous piece of
+// col / val, which the workgroup copies into LDS with coalesced loads (a lane reading ITS row's entries reads 4 / 8 bytes at
+// a stride of 28 / 56: 1.25 TB/s, 9.3 ms at 512^3) and every lane then walks its row there.  A piece that does not fit
+// (rows with long tails) is read from global memory as before.  (The copy alone: 10.3 ms; with the once-per-lane inserts
+// of add_once: 4.9 ms; a wave-private copy without the workgroup barriers: 5.0 ms -- the same.)
+constexpr int ANALYZE_CAP = 2560;
+template <typename V, typename P>
+__global__ __launch_bounds__(256)
+void analyze_fused_kernel(long long n, int w, const P *__restrict__ ptr, const int *__restrict__ col, const V *__restrict__ val,
+        int *gset_d, int *info_d, typename bits_of<V>::type *gset_v, int *info_v, int *max_col)
+{
+    typedef typename bits_of<V>::type B;
+    __shared__ int s_set[LOCAL_SLOTS];
+    __shared__ B s_vset[LOCAL_SLOTS];
+    __shared__ int s_over, s_count, s_vover, s_vcount, s_vskip;
+    collector<int, diagonal_keys::limit> cd{s_set, s_over, s_count};
+    collector<B, value_keys<V>::limit> cv{s_vset, s_vover, s_vcount};
+    __shared__ long long s_ptr[257];
+    __shared__ int s_c[ANALYZE_CAP];
+    __shared__ V s_v[ANALYZE_CAP];
+    const int t = threadIdx.x;
+    cd.init(info_d);
+    cv.init(info_v);
+    __syncthreads();
+    int m = -1;
+    int seen_d[8]; B seen_v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { seen_d[j] = set_key<int>::empty; seen_v[j] = set_key<B>::empty; }
+    for (long long r0 = (long long)blockIdx.x * 256; r0 < n; r0 += (long long)gridDim.x * 256) {
+        const int rows = (int)(n - r0 < 256 ? n - r0 : 256);
+        for (int k = t; k <= rows; k += 256) s_ptr[k] = (long long)ptr[r0 + k];
+        // more values than codes (a matrix with a coefficient per face says so within its first rows): the rest of the pass is
+        // about the diagonals and the largest column only -- the values, two thirds of the bytes, are not read any more
+        // (variable-coefficient 512^3: set-up 18.0 -> 17.1 ms -- the pass is not bound by its bytes either)
+        if (t == 0) s_vskip = cv.stopped(info_v) ? 1 : 0;
+        __syncthreads();
+        const long long e0 = s_ptr[0], cnt = s_ptr[rows] - e0;
+        const bool staged = cnt <= ANALYZE_CAP;                       // uniform
+        const bool vskip = s_vskip != 0;                              // uniform
+        if (staged) {
+            if (vskip) for (int k = t; k < (int)cnt; k += 256) s_c[k] = col[e0 + k];
+            else for (int k = t; k < (int)cnt; k += 256) { s_c[k] = col[e0 + k]; s_v[k] = val[e0 + k]; }
+        }
+        __syncthreads();
+        if (t < rows) {
+            const long long i = r0 + t, b = s_ptr[t], e = s_ptr[t + 1];
+            const bool dstop = cd.stopped(info_d);
+            const bool vstop = vskip || cv.stopped(info_v);
+            int last = set_key<int>::empty; B vlast = set_key<B>::empty;
+            const int nj = (int)(e - b < (long long)w ? e - b : (long long)w), off = (int)(b - e0);
+            for (int j = 0; j < nj; ++j) {
+                const int c = staged ? s_c[off + j] : col[b + j];
+                const V v = vstop ? V(0) : (staged ? s_v[off + j] : val[b + j]);
+                m = c > m ? c : m;
+                if (!dstop) add_once<diagonal_keys>(cd, info_d, c, i, j, last, seen_d);
+                if (!vstop) add_once<value_keys<V>>(cv, info_v, v, i, j, vlast, seen_v);
+            }
+        }
+        __syncthreads();                                               // the next 256 rows overwrite s_ptr / s_c / s_v
+    }
+    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_down(m, o, 64); m = u > m ? u : m; }
+    if ((t & 63) == 0 && m >= 0) atomicMax(max_col, m);
+    __syncthreads();
+    cd.merge(gset_d, info_d);
+    cv.merge(gset_v, info_v);
+}
+
+// ---- set-up: the fills of the two coded storages ----------------------------------------
+// position of `key` in a sorted table of `count` entries (binary search), -1 if it is not there
+template <typename T>
+__device__ __forceinline__ int table_find(const T *s_table, int count, T key) {
+    int lo = 0, hi = count;                      // first table entry >= key
+    while (lo < hi) { int mid = (lo + hi) >> 1; if (s_table[mid] < key) lo = mid + 1; else hi = mid; }
+    return (lo < count && s_table[lo] == key) ? lo : -1;
+}
+
+// code of a diagonal, S8_PAD if it is not in the table
 __device__ __forceinline__ unsigned delta_code(const int *s_table, int ndeltas, long long dl) {
     if (dl < INT_MIN || dl > INT_MAX) return S8_PAD;
-    const int d = (int)dl;
-    int lo = 0, hi = ndeltas;                    // first table entry >= d
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (s_table[mid] < d) lo = mid + 1; else hi = mid; }
-    return (lo < ndeltas && s_table[lo] == d) ? (unsigned)lo : (unsigned)S8_PAD;
+    const int p = table_find(s_table, ndeltas, (int)dl);
+    return p >= 0 ? (unsigned)p : S8_PAD;
 }
 
 // padding code of the empty half of a column whose other half holds column index `c` of row half `q`:
@@ -193,32 +343,7 @@ __device__ __forceinline__ unsigned delta_code(const int *s_table, int ndeltas, 
 __device__ __forceinline__ unsigned pad_code(int partner_col, int partner_q, int max_col) {
     if (partner_col < 0) return S8_PAD;                                 // both halves empty
     const long long first = (long long)partner_col - partner_q;        // element the 16-byte load starts at
-    return (first >= 0 && first + 1 <= max_col) ? (unsigned)S8_PAD : S8_PAD_UNSAFE;
-}
-
-// The entries of the 128 rows a wave fills (64 row pairs) are one contiguous piece of col / val: the wave copies it into its own
-// LDS region with coalesced loads -- no workgroup barrier, the waves keep their own pace -- and merge, code look-ups and
-// stores work from there.  (History at 512^3, sell8v fill: every lane loading its pair's entries itself, 4 / 8 bytes at a
-// stride of 56 / 112, 8.8 ms; the same with the 512 rows of a slice copied by the whole workgroup behind barriers, 56 KiB
-// of LDS: 10.9 ms; this: see DESIGN.md 6.)  A piece beyond WAVE_CAP entries (long rows) is walked in global memory.
-constexpr int WAVE_CAP = 1024;
-template <typename V>
-__device__ __forceinline__ bool wave_stage(const int *__restrict__ col, const V *__restrict__ val, long long b0_lane, long long e1_lane,
-        int *s_c, V *s_v, long long &e0)
-{
-    const int lane = threadIdx.x & 63;
-    // lanes past the end of the matrix hold b = e = 0: the piece is [first lane's begin, last REAL lane's end)
-    const unsigned long long real = __ballot(e1_lane > 0 || b0_lane > 0);
-    long long lo = b0_lane, hi = e1_lane;
-    e0 = __shfl(lo, 0, 64);                                         // lane 0 is real whenever any lane is
-    const int lastl = real ? 63 - __builtin_clzll(real) : 0;
-    const long long end = __shfl(hi, lastl, 64);
-    const long long cnt = end - e0;
-    if (cnt > WAVE_CAP || cnt < 0) return false;                     // uniform
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();       // the previous trip's reads of this region are done
-    for (int k = lane; k < (int)cnt; k += 64) { s_c[k] = col[e0 + k]; s_v[k] = val[e0 + k]; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    return true;
+    return (first >= 0 && first + 1 <= max_col) ? S8_PAD : S8_PAD_UNSAFE;
 }
 
 // One LDS counter bump per entry -- but the lanes of a wave that walk the rows of one stencil hold the SAME code in the same
@@ -233,32 +358,121 @@ __device__ __forceinline__ void count_code(unsigned *s_cnt, unsigned code) {
     }
 }
 
-// table: sorted diagonals (ndeltas valid entries); counts[256]: entries per code; info[1]: set if a diagonal is missing;
-// max_col: largest column index of the ELL part (ell_max_col_kernel)
-template <typename V, typename P, bool STAGED>
+// What a fill does with the VALUES -- the storage policy of coded_fill_kernel.  It says what is staged per entry and in which
+// LDS type, how a column's two entries reach the slice, and how far apart the slices are.  It travels as a kernel argument;
+// attach() takes the kernel's LDS (this wave's staging region, the table) before the kernel's first barrier.  An `entry` is a
+// value on its way from the CSR arrays (direct) or the staging region (staged) to emit().
+//
+// SELL8: the values themselves, j-major behind the diagonal codes of the slice.
+template <typename V> struct stored_values {
+    typedef V value;
+    typedef V staged_type;                                                  // staged per entry: the value
+    typedef char bits; static constexpr int table_entries = 1;              // (no value table: the kernel's array is never touched)
+    typedef V entry;                                                        // the value; 0 for padding
+    V *s_v, *vp;                                                            // the staging region; this lane's rows in the value plane
+    static __device__ __forceinline__ long long slice_stride(int w) { return slice_bytes(w, sizeof(V)); }
+    __device__ __forceinline__ void attach(V *staging, bits *) { s_v = staging; }
+    __device__ __forceinline__ void stage(int k, V v) const { s_v[k] = v; }
+    __device__ __forceinline__ entry staged(int k) const { return s_v[k]; }
+    static __device__ __forceinline__ entry direct(V v) { return v; }
+    static __device__ __forceinline__ entry none() { return V(0); }
+    __device__ __forceinline__ void begin_slice(char *slice, int wp, int t) { vp = reinterpret_cast<V *>(slice + (long long)wp * 1024) + 2 * t; }
+    __device__ __forceinline__ void emit(int j, bool inside, int q, bool, entry e, int *) const { if (inside) vp[(long long)j * S8_ROWS + q] = e; }
+};
+
+// SELL8V: a word of value codes next to every word of diagonal codes, 255 for padding (table entry 255 = 0.0).  This storage
+// does not need the values themselves: the lane that copies an entry into the staging region looks its value up in the sorted
+// table there and then and leaves a 2-byte code (0xffff: not in the table) -- 6 instead of 12 bytes of LDS per entry, 27 instead
+// of 53 KiB per workgroup, twice the waves per CU for a kernel whose waves are parked 73 % of their time
+// (profiles/r03_sq_setup.txt).  An entry that was not staged is looked up when it is emitted.
+template <typename V> struct coded_values {
+    const V *vtable; int nvalues;                                           // from the host: the sorted table (nvalues valid entries)
+    typedef V value;
+    typedef unsigned short staged_type;                                     // staged per entry: the value's code
+    typedef typename bits_of<V>::type bits; static constexpr int table_entries = 256;
+    struct entry { int code; V ev; };                                       // the code as staged (-1: not in the table), or -2 = look ev up
+    unsigned short *s_vc; bits *s_vtable;                                   // the staging region; the table's bit patterns
+    unsigned *vw; unsigned vword;                                           // this lane's word of the slice's value codes
+    static __device__ __forceinline__ long long slice_stride(int w) { return (long long)((w + 1) / 2) * 2048; }
+    __device__ __forceinline__ void attach(unsigned short *staging, bits *table) {
+        s_vc = staging; s_vtable = table;
+        V v = (int)threadIdx.x < nvalues ? vtable[threadIdx.x] : V(0); bits b; __builtin_memcpy(&b, &v, sizeof(bits));
+        s_vtable[threadIdx.x] = (int)threadIdx.x < nvalues ? b : ~bits(0);
+    }
+    __device__ __forceinline__ int find(V v) const { bits b; __builtin_memcpy(&b, &v, sizeof(bits)); return table_find(s_vtable, nvalues, b); }
+    __device__ __forceinline__ void stage(int k, V v) const { s_vc[k] = (unsigned short)find(v); }                   // (-1 -> 0xffff)
+    __device__ __forceinline__ entry staged(int k) const { return entry{(short)s_vc[k], V(0)}; }                      // (0xffff -> -1)
+    static __device__ __forceinline__ entry direct(V v) { return entry{-2, v}; }
+    static __device__ __forceinline__ entry none() { return entry{-2, V(0)}; }
+    __device__ __forceinline__ void begin_slice(char *slice, int wp, int t) { vw = reinterpret_cast<unsigned *>(slice) + t + wp * 256; vword = 0; }
+    __device__ __forceinline__ void emit(int j, bool, int q, bool has, entry e, int *info) {
+        unsigned vcode = 255;
+        if (has) {
+            const int p = e.code != -2 ? e.code : find(e.ev);
+            if (p >= 0) vcode = (unsigned)p; else atomicExch(&info[1], 1);
+        }
+        const int slot = (j & 1) * 2 + q;                                   // the byte of the code word
+        vword |= vcode << (8 * slot);
+        if (slot == 3) { vw[(j >> 1) * 256] = vword; vword = 0; }
+    }
+};
+
+// The entries of the 128 rows a wave fills (64 row pairs) are one contiguous piece of col / val: the wave copies it into its own
+// LDS region with coalesced loads -- no workgroup barrier, the waves keep their own pace -- and merge, code look-ups and
+// stores work from there.  (History at 512^3, sell8v fill: every lane loading its pair's entries itself, 4 / 8 bytes at a
+// stride of 56 / 112, 8.8 ms; the same with the 512 rows of a slice copied by the whole workgroup behind barriers, 56 KiB
+// of LDS: 10.9 ms; this: see DESIGN.md 6.)  A piece beyond WAVE_CAP entries (long rows) is walked in global memory.
+constexpr int WAVE_CAP = 1024;
+template <class Store>
+__device__ __forceinline__ bool wave_stage(const int *__restrict__ col, const typename Store::value *__restrict__ val, long long b0_lane, long long e1_lane,
+        int *s_c, const Store &st, long long &e0)
+{
+    const int lane = threadIdx.x & 63;
+    // lanes past the end of the matrix hold b = e = 0: the piece is [first lane's begin, last REAL lane's end)
+    const unsigned long long real = __ballot(e1_lane > 0 || b0_lane > 0);
+    long long lo = b0_lane, hi = e1_lane;
+    e0 = __shfl(lo, 0, 64);                                         // lane 0 is real whenever any lane is
+    const int lastl = real ? 63 - __builtin_clzll(real) : 0;
+    const long long end = __shfl(hi, lastl, 64);
+    const long long cnt = end - e0;
+    if (cnt > WAVE_CAP || cnt < 0) return false;                     // uniform
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();       // the previous trip's reads of this region are done
+    for (int k = lane; k < (int)cnt; k += 64) { s_c[k] = col[e0 + k]; st.stage(k, val[e0 + k]); }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return true;
+}
+
+// The fill of both coded storages; `st` says what becomes of the values.  table: sorted diagonals (ndeltas valid entries);
+// counts[256]: entries per code; info[1]: set if a diagonal (or, SELL8V, a value) is missing; max_col: largest column index of
+// the ELL part (ell_max_col_kernel).  STAGED (w <= 8): the entries of a wave's 128 rows are copied into its LDS region -- the
+// column indices, and what the storage stages of the values -- with coalesced loads (wave_stage); the merge, the code look-ups
+// and the stores work from there.  Not STAGED: these arrays are one element each, and the storage's table is all it holds.
+template <class Store, typename P, bool STAGED>
 __global__ __launch_bounds__(256)
-void sell8_fill_kernel(long long n, long long nslices, int w, int ndeltas,
-        const P *__restrict__ ptr, const int *__restrict__ col, const V *__restrict__ val,
+void coded_fill_kernel(Store st, long long n, long long nslices, int w, int ndeltas,
+        const P *__restrict__ ptr, const int *__restrict__ col, const typename Store::value *__restrict__ val,
         const int *__restrict__ table, const int *__restrict__ max_col_p, char *__restrict__ buf, unsigned long long *counts, int *info)
 {
     __shared__ int s_table[256];
     __shared__ unsigned s_cnt[256];
-    __shared__ int s_cw[STAGED ? 4 : 1][STAGED ? WAVE_CAP : 1];          // STAGED (w <= 8): the pair's entries in lane-private LDS slots (sell8v_fill_kernel)
-    __shared__ V s_vw[STAGED ? 4 : 1][STAGED ? WAVE_CAP : 1];
-    s_table[threadIdx.x] = threadIdx.x < ndeltas ? table[threadIdx.x] : INT_MAX;
+    __shared__ int s_cw[STAGED ? 4 : 1][STAGED ? WAVE_CAP : 1];
+    __shared__ typename Store::staged_type s_sw[STAGED ? 4 : 1][STAGED ? WAVE_CAP : 1];
+    __shared__ typename Store::bits s_vtable[Store::table_entries];
+    int *s_c = s_cw[STAGED ? threadIdx.x >> 6 : 0];
+    s_table[threadIdx.x] = (int)threadIdx.x < ndeltas ? table[threadIdx.x] : INT_MAX;
+    st.attach(s_sw[STAGED ? threadIdx.x >> 6 : 0], s_vtable);
     s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const int max_col = *max_col_p;
     const int wp = (w + 1) / 2;
-    const int lt = threadIdx.x;
     // one lane per row PAIR (the unit the product kernel reads)
     for (long long pr = (long long)blockIdx.x * blockDim.x + threadIdx.x; pr < nslices * (S8_ROWS / 2);
          pr += (long long)gridDim.x * blockDim.x) {
         const long long s = pr / (S8_ROWS / 2);
         const int t = (int)(pr % (S8_ROWS / 2));
-        char *slice = buf + s * slice_bytes(w, sizeof(V));
+        char *slice = buf + s * Store::slice_stride(w);
         unsigned *cw = reinterpret_cast<unsigned *>(slice) + t;
-        V *vp = reinterpret_cast<V *>(slice + (long long)wp * 1024) + 2 * t;
+        st.begin_slice(slice, wp, t);
         long long b[2] = {0, 0}, e[2] = {0, 0};
         const long long i = s * S8_ROWS + 2 * t;
         for (int q = 0; q < 2; ++q) if (i + q < n) { b[q] = ptr[i + q]; e[q] = ptr[i + q + 1]; }
@@ -266,11 +480,10 @@ void sell8_fill_kernel(long long n, long long nslices, int w, int ndeltas,
         pair_walk pw;
         pair_merge<diag_lds> pm;
         bool staged = false, same = false;
-        int *s_c = s_cw[STAGED ? lt >> 6 : 0]; V *s_v = s_vw[STAGED ? lt >> 6 : 0];
         if constexpr (STAGED) {
             long long e0;
             // (the previous trip's reads of this wave's region are done: same wave, program order)
-            staged = wave_stage<V>(col, val, b[0], e[1] > 0 ? e[1] : e[0], s_c, s_v, e0);
+            staged = wave_stage(col, val, b[0], e[1] > 0 ? e[1] : e[0], s_c, st, e0);
             if (staged) {
                 diag_lds g; g.s = s_c; g.off[0] = (int)(b[0] - e0); g.off[1] = (int)(b[1] - e0); g.row = i;
                 pm.d = g;
@@ -289,15 +502,16 @@ void sell8_fill_kernel(long long n, long long nslices, int w, int ndeltas,
             unsigned word = 0;
             for (int jj = 0; jj < 2; ++jj) {
                 const int j = 2 * jp + jj;
-                int ec[2] = {-1, -1}; V ev[2] = {V(0), V(0)}; bool has[2] = {false, false};
+                int ec[2] = {-1, -1}; bool has[2] = {false, false};                 // the column's two entries: column index ...
+                typename Store::entry ev[2] = {Store::none(), Store::none()};      // ... and value
                 if (j < w) {
                     if (staged) {
                         int k[2];
                         if (same) k[0] = k[1] = j < n0 ? j : -1; else pm.next(k[0], k[1]);
-                        for (int q = 0; q < 2; ++q) if (k[q] >= 0) { has[q] = true; ec[q] = s_c[pm.d.off[q] + k[q]]; ev[q] = s_v[pm.d.off[q] + k[q]]; }
+                        for (int q = 0; q < 2; ++q) if (k[q] >= 0) { has[q] = true; ec[q] = s_c[pm.d.off[q] + k[q]]; ev[q] = st.staged(pm.d.off[q] + k[q]); }
                     } else {
                         long long en[2]; pw.next(en[0], en[1]);
-                        for (int q = 0; q < 2; ++q) if (en[q] >= 0) { has[q] = true; ec[q] = col[en[q]]; ev[q] = val[en[q]]; }
+                        for (int q = 0; q < 2; ++q) if (en[q] >= 0) { has[q] = true; ec[q] = col[en[q]]; ev[q] = Store::direct(val[en[q]]); }
                     }
                 }
                 for (int q = 0; q < 2; ++q) {
@@ -308,7 +522,7 @@ void sell8_fill_kernel(long long n, long long nslices, int w, int ndeltas,
                         if (code != S8_PAD) count_code(s_cnt, code); else atomicExch(&info[1], 1);
                     } else code = pad_code(has[1 - q] ? ec[1 - q] : -1, 1 - q, max_col);
                     word |= code << (8 * (jj * 2 + q));
-                    if (j < w) vp[(long long)j * S8_ROWS + q] = ev[q];
+                    st.emit(j, j < w, q, has[q], ev[q], info);
                 }
             }
             cw[jp * 256] = word;
@@ -330,10 +544,6 @@ void sell8_fill_kernel(long long n, long long nslices, int w, int ndeltas,
 // Slice layout: ceil(w/2) KiB of diagonal codes, then ceil(w/2) KiB of value codes,
 // both packed as in SELL8.
 // ---------------------------------------------------------------------------
-template <typename V> struct bits_of;
-template <> struct bits_of<double> { typedef unsigned long long type; };
-template <> struct bits_of<float> { typedef unsigned type; };
-
 template <typename V, int W>
 __global__ __launch_bounds__(256)
 void sell8v_kernel(long long n, long long nslices, V alpha, int append, int ell_w,
@@ -1219,295 +1429,6 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
     }
 }
 
-// distinct value bit patterns of the ELL part: gset = HASH_SLOTS words (all-ones = empty), info as delta_collect_kernel
-template <typename B>
-__device__ __forceinline__ bool vset_insert(B *set, int slots, B v, bool *is_new) {
-    const B empty = ~B(0);
-    unsigned h = (unsigned)((unsigned long long)v * 0x9E3779B97F4A7C15ull >> 40) % (unsigned)slots;
-    for (int probe = 0; probe < slots; ++probe) {
-        B old = atomicCAS(&set[h], empty, v);
-        if (old == empty) { if (is_new) *is_new = true; return true; }
-        if (old == v) return true;
-        h = (h + 1) % (unsigned)slots;
-    }
-    return false;
-}
-
-template <typename V, typename P>
-__global__ __launch_bounds__(256)
-void value_collect_kernel(long long n, int w, const P *__restrict__ ptr, const V *__restrict__ val,
-        typename bits_of<V>::type *gset, int *info)
-{
-    typedef typename bits_of<V>::type B;
-    __shared__ B s_set[LOCAL_SLOTS];
-    __shared__ int s_over, s_count;
-    for (int k = threadIdx.x; k < LOCAL_SLOTS; k += blockDim.x) s_set[k] = ~B(0);
-    if (threadIdx.x == 0) { s_over = *(volatile int *)&info[1]; s_count = 0; }
-    __syncthreads();
-    // A matrix whose values are all different fills the set at once.  Stop at the 256th distinct value (a half-full
-    // table: short probe sequences), tell the other workgroups through the global flag, and do not merge: with the
-    // first version of this loop (probe until the 512-slot table is FULL, flag raised only at the end) the analysis of
-    // the 512^3 variable-coefficient matrix took 143 ms (profiles/r02_*cpp_kernel_stats.csv).
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        if (*(volatile int *)&s_over || *(volatile int *)&info[1]) break;
-        const P b = ptr[i], e = ptr[i + 1];
-        B last = ~B(0);
-        for (int j = 0; j < w && b + j < e; ++j) {
-            B bits; V v = val[b + j];
-            __builtin_memcpy(&bits, &v, sizeof(B));
-            if (bits == ~B(0)) { s_over = 1; continue; }          // the one pattern that cannot be stored (a NaN payload)
-            if (bits == last) continue;
-            last = bits;
-            bool fresh = false;
-            if (!vset_insert<B>(s_set, LOCAL_SLOTS, bits, &fresh)) s_over = 1;
-            else if (fresh && atomicAdd(&s_count, 1) >= 255) { s_over = 1; atomicExch(&info[1], 1); }
-        }
-    }
-    __syncthreads();
-    if (s_over) { if (threadIdx.x == 0) atomicExch(&info[1], 1); return; }
-    for (int k = threadIdx.x; k < LOCAL_SLOTS; k += blockDim.x) {
-        if (s_set[k] == ~B(0)) continue;
-        bool is_new = false;
-        if (!vset_insert<B>(gset, HASH_SLOTS, s_set[k], &is_new)) atomicExch(&info[1], 1);
-        else if (is_new) atomicAdd(&info[0], 1);
-    }
-    if (threadIdx.x == 0 && s_over) atomicExch(&info[1], 1);
-}
-
-// vtable: sorted value bit patterns (nvalues valid entries)
-// Diagonals, values and the largest column of the ELL part in ONE pass over the CSR arrays (round 3: delta_collect +
-// value_collect + ell_max_col read ptr / col / val three times, 12 ms of the 512^3 set-up).  Same sets, same overflow rules
-// as the two collect kernels.  A workgroup takes 256 consecutive rows at a time; their entries are one contiguous piece of
-// col / val, which the workgroup copies into LDS with coalesced loads (a lane reading ITS row's entries reads 4 / 8 bytes at
-// a stride of 28 / 56: 1.25 TB/s, 9.3 ms at 512^3) and every lane then walks its row there.  A piece that does not fit
-// (rows with long tails) is read from global memory as before.  (The copy alone: 10.3 ms; with the once-per-lane inserts
-// below: 4.9 ms; a wave-private copy without the workgroup barriers: 5.0 ms -- the same.)
-constexpr int ANALYZE_CAP = 2560;
-template <typename V, typename P>
-__global__ __launch_bounds__(256)
-void analyze_fused_kernel(long long n, int w, const P *__restrict__ ptr, const int *__restrict__ col, const V *__restrict__ val,
-        int *gset_d, int *info_d, typename bits_of<V>::type *gset_v, int *info_v, int *max_col)
-{
-    typedef typename bits_of<V>::type B;
-    __shared__ int s_set[LOCAL_SLOTS];
-    __shared__ B s_vset[LOCAL_SLOTS];
-    __shared__ int s_over, s_count, s_vover, s_vcount, s_vskip;
-    __shared__ long long s_ptr[257];
-    __shared__ int s_c[ANALYZE_CAP];
-    __shared__ V s_v[ANALYZE_CAP];
-    const int t = threadIdx.x;
-    for (int k = t; k < LOCAL_SLOTS; k += blockDim.x) { s_set[k] = EMPTY; s_vset[k] = ~B(0); }
-    if (t == 0) { s_over = *(volatile int *)&info_d[1]; s_count = 0; s_vover = *(volatile int *)&info_v[1]; s_vcount = 0; }
-    __syncthreads();
-    int m = -1;
-    int seen_d[8]; B seen_v[8];                                  // what this lane inserted last at entry position j (both sets only grow)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { seen_d[j] = EMPTY; seen_v[j] = ~B(0); }
-    for (long long r0 = (long long)blockIdx.x * 256; r0 < n; r0 += (long long)gridDim.x * 256) {
-        const int rows = (int)(n - r0 < 256 ? n - r0 : 256);
-        for (int k = t; k <= rows; k += 256) s_ptr[k] = (long long)ptr[r0 + k];
-        // more values than codes (a matrix with a coefficient per face says so within its first rows): the rest of the pass is
-        // about the diagonals and the largest column only -- the values, two thirds of the bytes, are not read any more
-        // (variable-coefficient 512^3: set-up 18.0 -> 17.1 ms -- the pass is not bound by its bytes either)
-        if (t == 0) s_vskip = (*(volatile int *)&s_vover || *(volatile int *)&info_v[1]) ? 1 : 0;
-        __syncthreads();
-        const long long e0 = s_ptr[0], cnt = s_ptr[rows] - e0;
-        const bool staged = cnt <= ANALYZE_CAP;                       // uniform
-        const bool vskip = s_vskip != 0;                              // uniform
-        if (staged) {
-            if (vskip) for (int k = t; k < (int)cnt; k += 256) s_c[k] = col[e0 + k];
-            else for (int k = t; k < (int)cnt; k += 256) { s_c[k] = col[e0 + k]; s_v[k] = val[e0 + k]; }
-        }
-        __syncthreads();
-        if (t < rows) {
-            const long long i = r0 + t, b = s_ptr[t], e = s_ptr[t + 1];
-            const bool dstop = *(volatile int *)&s_over || *(volatile int *)&info_d[1];
-            const bool vstop = vskip || *(volatile int *)&s_vover || *(volatile int *)&info_v[1];
-            int last = EMPTY; B vlast = ~B(0);
-            const int nj = (int)(e - b < (long long)w ? e - b : (long long)w), off = (int)(b - e0);
-            for (int j = 0; j < nj; ++j) {
-                const int c = staged ? s_c[off + j] : col[b + j];
-                const V v = vstop ? V(0) : (staged ? s_v[off + j] : val[b + j]);
-                m = c > m ? c : m;
-                if (!dstop) {
-                    const long long dl = (long long)c - i;
-                    if (dl <= INT_MIN || dl > INT_MAX) s_over = 1;
-                    else if ((int)dl != last && !(j < 8 && (int)dl == seen_d[j])) {
-                        // (a lane of a structured matrix meets the same diagonal at the same place of every row: what it has
-                        // inserted once it does not insert again -- 64 lanes inserting the same 7 diagonals per row were
-                        // 64-way conflicts on the LDS set: the kernel was bound by them, not by its loads)
-                        last = (int)dl;
-                        if (j < 8) seen_d[j] = last;
-                        bool fresh = false;
-                        if (!set_insert(s_set, LOCAL_SLOTS, last, &fresh)) s_over = 1;
-                        else if (fresh && atomicAdd(&s_count, 1) >= 254) { s_over = 1; atomicExch(&info_d[1], 1); }
-                    }
-                }
-                if (!vstop) {
-                    B bits; __builtin_memcpy(&bits, &v, sizeof(B));
-                    if (bits == ~B(0)) s_vover = 1;
-                    else if (bits != vlast && !(j < 8 && bits == seen_v[j])) {
-                        vlast = bits;
-                        if (j < 8) seen_v[j] = bits;
-                        bool fresh = false;
-                        if (!vset_insert<B>(s_vset, LOCAL_SLOTS, bits, &fresh)) s_vover = 1;
-                        else if (fresh && atomicAdd(&s_vcount, 1) >= 255) { s_vover = 1; atomicExch(&info_v[1], 1); }
-                    }
-                }
-            }
-        }
-        __syncthreads();                                               // the next 256 rows overwrite s_ptr / s_c / s_v
-    }
-    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_down(m, o, 64); m = u > m ? u : m; }
-    if ((t & 63) == 0 && m >= 0) atomicMax(max_col, m);
-    __syncthreads();
-    if (s_over) { if (t == 0) atomicExch(&info_d[1], 1); }
-    else
-        for (int k = t; k < LOCAL_SLOTS; k += blockDim.x) {
-            if (s_set[k] == EMPTY) continue;
-            bool is_new = false;
-            if (!set_insert(gset_d, HASH_SLOTS, s_set[k], &is_new)) atomicExch(&info_d[1], 1);
-            else if (is_new) atomicAdd(&info_d[0], 1);
-        }
-    if (s_vover) { if (t == 0) atomicExch(&info_v[1], 1); }
-    else
-        for (int k = t; k < LOCAL_SLOTS; k += blockDim.x) {
-            if (s_vset[k] == ~B(0)) continue;
-            bool is_new = false;
-            if (!vset_insert<B>(gset_v, HASH_SLOTS, s_vset[k], &is_new)) atomicExch(&info_v[1], 1);
-            else if (is_new) atomicAdd(&info_v[0], 1);
-        }
-}
-
-// The same for the value-coded storage, which does not need the values themselves: the lane that copies an entry looks its
-// value up in the sorted table there and then and leaves a 2-byte code (0xffff: not in the table) -- 6 instead of 12 bytes
-// of LDS per entry, 27 instead of 53 KiB per workgroup, twice the waves per CU for a kernel whose waves are parked 73 % of
-// their time (profiles/r03_sq_setup.txt).
-template <typename V>
-__device__ __forceinline__ bool wave_stage_codes(const int *__restrict__ col, const V *__restrict__ val, long long b0_lane, long long e1_lane,
-        int *s_c, unsigned short *s_vc, const typename bits_of<V>::type *s_vtable, int nvalues, long long &e0)
-{
-    typedef typename bits_of<V>::type B;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long real = __ballot(e1_lane > 0 || b0_lane > 0);
-    long long lo_ = b0_lane, hi_ = e1_lane;
-    e0 = __shfl(lo_, 0, 64);
-    const int lastl = real ? 63 - __builtin_clzll(real) : 0;
-    const long long end = __shfl(hi_, lastl, 64);
-    const long long cnt = end - e0;
-    if (cnt > WAVE_CAP || cnt < 0) return false;                     // uniform
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();       // the previous trip's reads of this region are done
-    for (int k = lane; k < (int)cnt; k += 64) {
-        s_c[k] = col[e0 + k];
-        const V v = val[e0 + k];
-        B bits; __builtin_memcpy(&bits, &v, sizeof(B));
-        int lo = 0, hi = nvalues;
-        while (lo < hi) { int mid = (lo + hi) >> 1; if (s_vtable[mid] < bits) lo = mid + 1; else hi = mid; }
-        s_vc[k] = (lo < nvalues && s_vtable[lo] == bits) ? (unsigned short)lo : (unsigned short)0xffffu;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    return true;
-}
-
-// STAGED (w <= 8): the entries of a wave's 128 rows are copied into its LDS region with coalesced loads (wave_stage_codes);
-// the merge, the code look-ups and the stores work from there.
-template <typename V, typename P, bool STAGED>
-__global__ __launch_bounds__(256)
-void sell8v_fill_kernel(long long n, long long nslices, int w, int ndeltas, int nvalues,
-        const P *__restrict__ ptr, const int *__restrict__ col, const V *__restrict__ val,
-        const int *__restrict__ table, const V *__restrict__ vtable, const int *__restrict__ max_col_p,
-        char *__restrict__ buf, unsigned long long *counts, int *info)
-{
-    typedef typename bits_of<V>::type B;
-    __shared__ int s_table[256];
-    __shared__ B s_vtable[256];
-    __shared__ unsigned s_cnt[256];
-    __shared__ int s_cw[STAGED ? 4 : 1][STAGED ? WAVE_CAP : 1];
-    __shared__ unsigned short s_vcw[STAGED ? 4 : 1][STAGED ? WAVE_CAP : 1];     // value CODES of the staged entries (wave_stage_codes)
-    s_table[threadIdx.x] = threadIdx.x < ndeltas ? table[threadIdx.x] : INT_MAX;
-    { V v = threadIdx.x < nvalues ? vtable[threadIdx.x] : V(0); B b; __builtin_memcpy(&b, &v, sizeof(B)); s_vtable[threadIdx.x] = threadIdx.x < nvalues ? b : ~B(0); }
-    s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int max_col = *max_col_p;
-    const int wp = (w + 1) / 2;
-    const int lt = threadIdx.x;
-    for (long long pr = (long long)blockIdx.x * blockDim.x + threadIdx.x; pr < nslices * (S8_ROWS / 2);
-         pr += (long long)gridDim.x * blockDim.x) {
-        const long long s = pr / (S8_ROWS / 2);
-        const int t = (int)(pr % (S8_ROWS / 2));
-        unsigned *cw = reinterpret_cast<unsigned *>(buf + s * ((long long)wp * 2048)) + t;
-        unsigned *vw = cw + wp * 256;
-        long long b[2] = {0, 0}, e[2] = {0, 0};
-        const long long i = s * S8_ROWS + 2 * t;
-        for (int q = 0; q < 2; ++q) if (i + q < n) { b[q] = ptr[i + q]; e[q] = ptr[i + q + 1]; }
-        const int n0 = (int)min(e[0] - b[0], (long long)w), n1 = (int)min(e[1] - b[1], (long long)w);
-        pair_walk pw;
-        pair_merge<diag_lds> pm;
-        bool staged = false, same = false;
-        int *s_c = s_cw[STAGED ? lt >> 6 : 0]; unsigned short *s_vc = s_vcw[STAGED ? lt >> 6 : 0];
-        if constexpr (STAGED) {
-            long long e0;
-            // (the previous trip's reads of this wave's region are done: same wave, program order)
-            staged = wave_stage_codes<V>(col, val, b[0], e[1] > 0 ? e[1] : e[0], s_c, s_vc, s_vtable, nvalues, e0);
-            if (staged) {
-                diag_lds g; g.s = s_c; g.off[0] = (int)(b[0] - e0); g.off[1] = (int)(b[1] - e0); g.row = i;
-                pm.d = g;
-                // the common pair: both rows hold the same diagonals in the same order (column of row 2t + 1 = column of
-                // row 2t, plus one) -- entry j of both goes to column j, no merge (a chain of dependent look-ups)
-                same = n0 == n1 && n0 <= 8;
-                if (same) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) if (k < n0 && s_c[g.off[0] + k] + 1 != s_c[g.off[1] + k]) same = false;
-                }
-                if (!same) pm.init(g, n0, n1, w);
-            }
-        }
-        if (!staged) pw.init(col, i, b[0], n0, b[1], n1, w);
-        for (int jp = 0; jp < wp; ++jp) {
-            unsigned word = 0, vword = 0;
-            for (int jj = 0; jj < 2; ++jj) {
-                const int j = 2 * jp + jj;
-                int ec[2] = {-1, -1}; V ev[2] = {V(0), V(0)}; bool has[2] = {false, false};      // the column's two entries: column index, value
-                unsigned sc[2] = {0x10000u, 0x10000u};                                          // ... or (staged) the value's code: 0x10000 = look ev up
-                if (j < w) {
-                    if (staged) {
-                        int k[2];
-                        if (same) k[0] = k[1] = j < n0 ? j : -1; else pm.next(k[0], k[1]);
-                        for (int q = 0; q < 2; ++q) if (k[q] >= 0) { has[q] = true; ec[q] = s_c[pm.d.off[q] + k[q]]; sc[q] = s_vc[pm.d.off[q] + k[q]]; }
-                    } else {
-                        long long en[2]; pw.next(en[0], en[1]);
-                        for (int q = 0; q < 2; ++q) if (en[q] >= 0) { has[q] = true; ec[q] = col[en[q]]; ev[q] = val[en[q]]; }
-                    }
-                }
-                for (int q = 0; q < 2; ++q) {
-                    unsigned code, vcode = 255;                     // value code of padding: table entry 255 = 0.0
-                    if (has[q]) {
-                        if (q == 1 && has[0] && ec[1] == ec[0] + 1) code = (word >> (8 * (jj * 2))) & 255u;     // the partner's diagonal: its code
-                        else code = delta_code(s_table, ndeltas, (long long)ec[q] - (i + q));
-                        if (code != S8_PAD) count_code(s_cnt, code); else atomicExch(&info[1], 1);
-                        if (sc[q] != 0x10000u) {                            // looked up when the entry was staged
-                            if (sc[q] != 0xffffu) vcode = sc[q]; else atomicExch(&info[1], 1);
-                        } else {
-                            B bits; V v = ev[q];
-                            __builtin_memcpy(&bits, &v, sizeof(B));
-                            int lo = 0, hi = nvalues;
-                            while (lo < hi) { int mid = (lo + hi) >> 1; if (s_vtable[mid] < bits) lo = mid + 1; else hi = mid; }
-                            if (lo < nvalues && s_vtable[lo] == bits) vcode = (unsigned)lo;
-                            else atomicExch(&info[1], 1);
-                        }
-                    } else code = pad_code(has[1 - q] ? ec[1 - q] : -1, 1 - q, max_col);
-                    word |= code << (8 * (jj * 2 + q));
-                    vword |= vcode << (8 * (jj * 2 + q));
-                }
-            }
-            cw[jp * 256] = word;
-            vw[jp * 256] = vword;
-        }
-    }
-    __syncthreads();
-    if (s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-}
-
 // how many entries of the CSR matrix lie on each diagonal of the table (for the traversal heuristic)
 template <typename P>
 __global__ __launch_bounds__(256)
@@ -1522,10 +1443,8 @@ void csr_delta_count_kernel(long long n, int w, int ndeltas, const P *__restrict
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const P b = ptr[i], e = ptr[i + 1];
         for (int j = 0; j < w && b + j < e; ++j) {
-            const int d = (int)((long long)col[b + j] - i);
-            int lo = 0, hi = ndeltas;
-            while (lo < hi) { int mid = (lo + hi) >> 1; if (s_table[mid] < d) lo = mid + 1; else hi = mid; }
-            if (lo < ndeltas && s_table[lo] == d) atomicAdd(&s_cnt[lo], 1u);
+            const int p = table_find(s_table, ndeltas, (int)((long long)col[b + j] - i));
+            if (p >= 0) atomicAdd(&s_cnt[p], 1u);
         }
     }
     __syncthreads();
@@ -1620,11 +1539,11 @@ void strip_traversal(int64_t n, const std::vector<int> &table, const std::vector
 }
 
 // What the fills of the two coded storages share.  Scratch: [counts of the table's diagonals: 256 x 8 bytes | info: [0] unused, [1] error flag,
-// [2] largest ELL column]; the largest column is uploaded where the caller knows it and searched for otherwise; fill(STAGED, grid, ns, counts, info)
-// launches the fill kernel; then the copies back, the verdict on the error flag (not_in_table: the caller's message) and the strip traversal.
-template <typename P, class Fill>
-int coded_fill(int dev, hipStream_t s, int64_t n, const P *ptr, const int *col, int64_t w, const int *deltas, int ndeltas, vexhip_traversal *trav,
-        int64_t known_max_col, int64_t *max_col, const char *not_in_table, Fill &&fill)
+// [2] largest ELL column]; the largest column is uploaded where the caller knows it and searched for otherwise; the fill kernel of the storage
+// policy `st`; then the copies back, the verdict on the error flag (not_in_table: the caller's message) and the strip traversal.
+template <class Store, typename P>
+int coded_fill(int dev, hipStream_t s, Store st, int64_t n, const P *ptr, const int *col, const typename Store::value *val, int64_t w, const int *deltas, int ndeltas,
+        void *buf, vexhip_traversal *trav, int64_t known_max_col, int64_t *max_col, const char *not_in_table)
 {
     VEXHIP_SET_DEVICE(dev);
     const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
@@ -1640,7 +1559,10 @@ int coded_fill(int dev, hipStream_t s, int64_t n, const P *ptr, const int *col, 
         VEXHIP_TRY(hipMemsetAsync(dinfo + 2, 0xff, sizeof(int), s));
         ell_max_col_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, dinfo + 2);
     }
-    with_bool(w <= 8, [&](auto STAGED) { fill(STAGED, grid_for(dev, ns * (S8_ROWS / 2)), ns, dcounts.p, dinfo); });
+    with_bool(w <= 8, [&](auto STAGED) {
+        coded_fill_kernel<Store, P, STAGED()><<<grid_for(dev, ns * (S8_ROWS / 2)), 256, 0, s>>>(st, n, ns, (int)w, ndeltas, ptr, col, val, deltas, dinfo + 2,
+                static_cast<char *>(buf), dcounts.p, dinfo);
+    });
     std::vector<unsigned long long> counts(256);
     std::vector<int> table(ndeltas);
     int hinfo[3] = {0, 0, -1};
@@ -1655,30 +1577,51 @@ int coded_fill(int dev, hipStream_t s, int64_t n, const P *ptr, const int *col, 
     return 0;
 }
 
-// A hash set collected on the device, copied to the host (HASH_SLOTS slots, `empty` where nothing is; count / overflow: the set's own info) ->
-// the table the kernels search: sorted, `pad` behind the last entry, 256 entries uploaded to table_dev; *entries = their number.  A set that is no
-// table's (overflow, more than max_entries, none) leaves *entries and table_dev as they are.
-template <typename T>
-int upload_table(hipStream_t s, const T *slots, T empty, T pad, int count, int overflow, int max_entries, const char *inconsistent, void *table_dev, int *entries)
+// The round trip of a device set: HASH_SLOTS keys and the two info words (count, overflow) behind them, in `bytes` of the caller's device
+// memory (aligned for K).  init: every key empty, the info zero; the collecting kernel takes keys / info; fetch + a stream synchronisation:
+// host holds the keys, count() and overflow() the info.
+template <typename K>
+struct device_set {
+    static constexpr size_t bytes = sizeof(K) * HASH_SLOTS + 2 * sizeof(int);
+    K *keys = nullptr; int *info = nullptr;
+    std::vector<K> host = std::vector<K>(HASH_SLOTS + 2 * sizeof(int) / sizeof(K));      // (the info words travel in the same copy)
+    int init(hipStream_t s, void *mem) {
+        keys = static_cast<K *>(mem); info = reinterpret_cast<int *>(keys + HASH_SLOTS);
+        // (either empty marker is one 32-bit word, repeated: INT_MIN, all-ones)
+        VEXHIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(keys), (int)(unsigned)set_key<K>::empty, sizeof(K) / 4 * HASH_SLOTS, s));
+        VEXHIP_TRY(hipMemsetAsync(info, 0, 2 * sizeof(int), s));
+        return 0;
+    }
+    int fetch(hipStream_t s) { VEXHIP_TRY(hipMemcpyAsync(host.data(), keys, bytes, hipMemcpyDeviceToHost, s)); return 0; }
+    int word(int k) const { int v; std::memcpy(&v, reinterpret_cast<const char *>(host.data() + HASH_SLOTS) + k * sizeof(int), sizeof(int)); return v; }
+    int count() const { return word(0); }
+    int overflow() const { return word(1); }
+};
+
+// A fetched set -> the table the kernels search: sorted, `pad` behind the last entry, 256 entries uploaded to table_dev; *entries = their
+// number.  A set that is no table's (overflow, more than max_entries, none) leaves *entries and table_dev as they are.
+template <typename K>
+int upload_table(hipStream_t s, const device_set<K> &set, K pad, int max_entries, const char *inconsistent, void *table_dev, int *entries)
 {
-    if (overflow != 0 || count > max_entries || count < 1) return 0;
-    std::vector<T> table;
-    for (int k = 0; k < HASH_SLOTS; ++k) if (slots[k] != empty) table.push_back(slots[k]);
+    const int count = set.count();
+    if (set.overflow() != 0 || count > max_entries || count < 1) return 0;
+    std::vector<K> table;
+    for (int k = 0; k < HASH_SLOTS; ++k) if (set.host[k] != set_key<K>::empty) table.push_back(set.host[k]);
     std::sort(table.begin(), table.end());                                    // (values: by bit pattern, what the fill kernel searches)
     if ((int)table.size() != count) return fail(__FILE__, __LINE__, inconsistent);
     table.resize(256, pad);
-    VEXHIP_TRY(hipMemcpyAsync(table_dev, table.data(), sizeof(T) * 256, hipMemcpyHostToDevice, s));
+    VEXHIP_TRY(hipMemcpyAsync(table_dev, table.data(), sizeof(K) * 256, hipMemcpyHostToDevice, s));
     VEXHIP_TRY(hipStreamSynchronize(s));
     *entries = count;
     return 0;
 }
-inline int upload_deltas(hipStream_t s, const int *set, int32_t *deltas, int *ndeltas) {      // set: HASH_SLOTS slots, count, overflow; codes 254 and 255 are padding
-    return upload_table<int>(s, set, EMPTY, INT_MAX, set[HASH_SLOTS], set[HASH_SLOTS + 1], 254, "diagonal set is inconsistent", deltas, ndeltas);
+inline int upload_deltas(hipStream_t s, const device_set<int> &set, int32_t *deltas, int *ndeltas) {      // codes 254 and 255 are padding
+    return upload_table<int>(s, set, INT_MAX, diagonal_keys::limit, "diagonal set is inconsistent", deltas, ndeltas);
 }
 template <typename V>
-int upload_values(hipStream_t s, const typename bits_of<V>::type *set, const int (&info)[2], V *values, int *nvalues) {    // 0.0 behind the last value: code 255 reads it
+int upload_values(hipStream_t s, const device_set<typename bits_of<V>::type> &set, V *values, int *nvalues) {    // 0.0 behind the last value: code 255 reads it
     typedef typename bits_of<V>::type B;
-    return upload_table<B>(s, set, ~B(0), B(0), info[0], info[1], 255, "value set is inconsistent", values, nvalues);
+    return upload_table<B>(s, set, B(0), value_keys<V>::limit, "value set is inconsistent", values, nvalues);
 }
 
 } // namespace
@@ -1693,10 +1636,8 @@ int sell8_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, c
     if (n == 0) return 0;
     VEXHIP_REQUIRE(ptr && col && val && deltas && buf, "NULL argument");
     hipStream_t s = as_stream(stream);
-    return coded_fill(dev, s, n, ptr, col, w, deltas, ndeltas, trav, known_max_col, max_col, "SELL8 fill: the matrix uses a diagonal that is not in the table",
-            [&](auto STAGED, int grid, long long ns, unsigned long long *dcounts, int *dinfo) {
-                sell8_fill_kernel<V, P, STAGED()><<<grid, 256, 0, s>>>(n, ns, (int)w, ndeltas, ptr, col, val, deltas, dinfo + 2, static_cast<char *>(buf), dcounts, dinfo);
-            });
+    return coded_fill(dev, s, stored_values<V>{}, n, ptr, col, val, w, deltas, ndeltas, buf, trav, known_max_col, max_col,
+            "SELL8 fill: the matrix uses a diagonal that is not in the table");
 }
 
 template <typename V>
@@ -1740,19 +1681,14 @@ int sell8v_analyze(int dev, void *stream, int64_t n, const P *ptr, const V *val,
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
     dev_buf<char> d;
-    VEXHIP_TRY(d.alloc(sizeof(B) * HASH_SLOTS + 2 * sizeof(int)));
-    B *dset = reinterpret_cast<B *>(d.p);
-    int *dinfo = reinterpret_cast<int *>(dset + HASH_SLOTS);
-    VEXHIP_TRY(hipMemsetAsync(dset, 0xff, sizeof(B) * HASH_SLOTS, s));
-    VEXHIP_TRY(hipMemsetAsync(dinfo, 0, 2 * sizeof(int), s));
-    value_collect_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, val, dset, dinfo);
-    std::vector<B> host(HASH_SLOTS);
-    int hinfo[2] = {0, 0};
-    VEXHIP_TRY(hipMemcpyAsync(host.data(), dset, sizeof(B) * HASH_SLOTS, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(hinfo, dinfo, sizeof(hinfo), hipMemcpyDeviceToHost, s));
+    device_set<B> set;
+    VEXHIP_TRY(d.alloc(set.bytes));
+    if (int rc = set.init(s, d.p)) return rc;
+    collect_kernel<value_keys<V>, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, val, set.keys, set.info);
+    if (int rc = set.fetch(s)) return rc;
     VEXHIP_TRY(hipStreamSynchronize(s));
     VEXHIP_TRY(d.free_now());
-    return upload_values<V>(s, host.data(), hinfo, values, nvalues);          // too many distinct values: they stay as they are
+    return upload_values<V>(s, set, values, nvalues);                         // too many distinct values: they stay as they are
 }
 
 // deltas[256] / values[256]: device tables as the two separate analyses write them; *ndeltas / *nvalues = -1 when not applicable
@@ -1765,39 +1701,33 @@ int analyze_fused(int dev, void *stream, int64_t n, const P *ptr, const int *col
     if (n <= 0 || w < 1) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    // [int set: HASH_SLOTS + 2 info][value set: HASH_SLOTS B + 2 int info][max col]
-    const size_t dbytes = sizeof(int) * (HASH_SLOTS + 2), vbytes = sizeof(B) * HASH_SLOTS + 2 * sizeof(int);
+    // one allocation: [diagonal set][value set, 16-byte aligned][max col]
+    device_set<int> dset;
+    device_set<B> vset;
+    const size_t voff = (dset.bytes + 15) / 16 * 16;
     dev_buf<char> d;
     setup_trace trace(s);
-    VEXHIP_TRY(d.alloc(dbytes + vbytes + sizeof(int) + 64));
+    VEXHIP_TRY(d.alloc(voff + vset.bytes + sizeof(int)));
     trace.mark("  fused: hipMalloc");
-    int *dset = reinterpret_cast<int *>(d.p);
-    B *vset = reinterpret_cast<B *>(d.p + ((dbytes + 15) / 16) * 16);
-    int *vinfo = reinterpret_cast<int *>(vset + HASH_SLOTS);
-    int *dmax = vinfo + 2;
-    std::vector<int> hd(HASH_SLOTS + 2, EMPTY);
-    hd[HASH_SLOTS] = 0; hd[HASH_SLOTS + 1] = 0;
-    VEXHIP_TRY(hipMemcpyAsync(dset, hd.data(), dbytes, hipMemcpyHostToDevice, s));
-    VEXHIP_TRY(hipMemsetAsync(vset, 0xff, sizeof(B) * HASH_SLOTS, s));
-    VEXHIP_TRY(hipMemsetAsync(vinfo, 0, 2 * sizeof(int), s));
+    int *dmax = reinterpret_cast<int *>(d.p + voff + vset.bytes);
+    int hmax = -1;
+    if (int rc = dset.init(s, d.p)) return rc;
+    if (int rc = vset.init(s, d.p + voff)) return rc;
     VEXHIP_TRY(hipMemsetAsync(dmax, 0xff, sizeof(int), s));
-    std::vector<B> hv(HASH_SLOTS);
-    int vi[2] = {0, 0}, hmax = -1;
-    trace.mark("  fused: H2D + memsets");
-    analyze_fused_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, val, dset, dset + HASH_SLOTS, vset, vinfo, dmax);
+    trace.mark("  fused: memsets");
+    analyze_fused_kernel<V, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, val, dset.keys, dset.info, vset.keys, vset.info, dmax);
     VEXHIP_LAUNCH_CHECK();
     trace.mark("  fused: kernel");
-    VEXHIP_TRY(hipMemcpyAsync(hd.data(), dset, dbytes, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(hv.data(), vset, sizeof(B) * HASH_SLOTS, hipMemcpyDeviceToHost, s));
-    VEXHIP_TRY(hipMemcpyAsync(vi, vinfo, sizeof(vi), hipMemcpyDeviceToHost, s));
+    if (int rc = dset.fetch(s)) return rc;
+    if (int rc = vset.fetch(s)) return rc;
     VEXHIP_TRY(hipMemcpyAsync(&hmax, dmax, sizeof(int), hipMemcpyDeviceToHost, s));
     VEXHIP_TRY(hipStreamSynchronize(s));
     trace.mark("  fused: D2H");
     (void)d.free_now();
     trace.mark("  fused: hipFree");
     *max_col = hmax;
-    if (int rc = upload_deltas(s, hd.data(), deltas, ndeltas)) return rc;
-    if (*ndeltas > 0) return upload_values<V>(s, hv.data(), vi, values, nvalues);   // value codes only where the diagonals have codes
+    if (int rc = upload_deltas(s, dset, deltas, ndeltas)) return rc;
+    if (*ndeltas > 0) return upload_values<V>(s, vset, values, nvalues);            // value codes only where the diagonals have codes
     return 0;
 }
 
@@ -1810,11 +1740,8 @@ int sell8v_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, 
     if (n == 0) return 0;
     VEXHIP_REQUIRE(ptr && col && val && deltas && values && buf, "NULL argument");
     hipStream_t s = as_stream(stream);
-    return coded_fill(dev, s, n, ptr, col, w, deltas, ndeltas, trav, known_max_col, max_col, "SELL8V fill: a diagonal or a value of the matrix is not in its table",
-            [&](auto STAGED, int grid, long long ns, unsigned long long *dcounts, int *dinfo) {
-                sell8v_fill_kernel<V, P, STAGED()><<<grid, 256, 0, s>>>(n, ns, (int)w, ndeltas, nvalues, ptr, col, val, deltas, values, dinfo + 2, static_cast<char *>(buf),
-                        dcounts, dinfo);
-            });
+    return coded_fill(dev, s, coded_values<V>{values, nvalues}, n, ptr, col, val, w, deltas, ndeltas, buf, trav, known_max_col, max_col,
+            "SELL8V fill: a diagonal or a value of the matrix is not in its table");
 }
 
 template <typename V>
@@ -1979,17 +1906,16 @@ int sell8_analyze(int dev, void *stream, int64_t n, const P *ptr, const int32_t 
     if (n <= 0 || w < 1) return 0;
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    dev_buf<int> d;
-    VEXHIP_TRY(d.alloc(HASH_SLOTS + 2));
-    std::vector<int> host(HASH_SLOTS + 2, EMPTY);
-    host[HASH_SLOTS] = 0; host[HASH_SLOTS + 1] = 0;
-    VEXHIP_TRY(hipMemcpyAsync(d.p, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, s));
-    delta_collect_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, d.p, d.p + HASH_SLOTS);
-    VEXHIP_TRY(hipMemcpyAsync(host.data(), d.p, sizeof(int) * host.size(), hipMemcpyDeviceToHost, s));
+    dev_buf<char> d;
+    device_set<int> set;
+    VEXHIP_TRY(d.alloc(set.bytes));
+    if (int rc = set.init(s, d.p)) return rc;
+    collect_kernel<diagonal_keys, P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, set.keys, set.info);
+    if (int rc = set.fetch(s)) return rc;
     VEXHIP_TRY(hipStreamSynchronize(s));
     VEXHIP_TRY(d.free_now());
-    if (env(ENV_VEXHIP_DEBUG)) std::fprintf(stderr, "sell8 analyze: count %d overflow %d\n", host[HASH_SLOTS], host[HASH_SLOTS + 1]);
-    return upload_deltas(s, host.data(), deltas, ndeltas);                    // (more than 254 diagonals: not a banded matrix)
+    if (env(ENV_VEXHIP_DEBUG)) std::fprintf(stderr, "sell8 analyze: count %d overflow %d\n", set.count(), set.overflow());
+    return upload_deltas(s, set, deltas, ndeltas);                            // (more than 254 diagonals: not a banded matrix)
 }
 
 int sell8_apply_halo(int dev, hipStream_t s, long long own_rows, double alpha, int append, int w, bool vcoded, const void *buf, const void *pool,
