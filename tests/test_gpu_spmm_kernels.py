@@ -1,5 +1,5 @@
 """Direct parity tests of the multi-right-hand-side SELL products of vexcl_amd/csrc/spmm.hip: `spmm_sell_kernel` (32-bit columns),
-`spmm_sell8_kernel` (diagonal codes, stored values) and `spmm_sell8v_kernel` (diagonal and value codes), fp64 and fp32, NR = 1..4
+`spmm_coded_kernel<..., VCODED = false>` (diagonal codes, stored values) and `<..., VCODED = true>` (diagonal and value codes), fp64 and fp32, NR = 1..4
 right-hand sides per launch and the split of 5..8 right-hand sides into two passes, the unrolled widths 3, 5, 7, 9 and the looping
 branch, with and without a CSR tail, and the slice-dictionary forms of the two coded kernels.
 

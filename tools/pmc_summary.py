@@ -21,7 +21,7 @@ def rows(pattern):
 
 
 def short(name):
-    for k in ("spmm_sell8_kernel", "spmm_sell_kernel", "sell8v_kernel", "sell8_kernel", "sell_kernel", "hell_kernel", "csr_stream_kernel", "reduce_stage1", "reduce_stage2", "poisson_kernel",
+    for k in ("spmm_coded_kernel", "spmm_sell8_kernel", "spmm_sell_kernel", "sell8v_kernel", "sell8_kernel", "sell_kernel", "hell_kernel", "csr_stream_kernel", "reduce_stage1", "reduce_stage2", "poisson_kernel",
               "hell_fill_kernel", "fill_hash_kernel"):
         if k in name:
             return k

@@ -22,6 +22,7 @@
 #include "storage.hpp"
 #include "lanes.hpp"
 #include "dispatch.hpp"
+#include "slices.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -42,23 +43,13 @@ thread_local int64_t g_fill_max_col = -1;
 
 namespace {
 
-constexpr int S8_ROWS = 512;
-constexpr unsigned S8_PAD_UNSAFE = 254;            // padding whose partner must not use the 16-byte load (pair kernels)
-constexpr unsigned S8_PAD = 255;                   // padding
-constexpr unsigned S8_FIRST_PAD = S8_PAD_UNSAFE;   // codes from here on are padding: a table holds at most 254 diagonals
 constexpr int HASH_SLOTS = 1024;
 constexpr int LOCAL_SLOTS = 512;          // per-workgroup set: twice the 255 entries a table may hold
 
-typedef double double2v __attribute__((ext_vector_type(2)));
-typedef float  float2v  __attribute__((ext_vector_type(2)));
-
 __host__ __device__ inline long long slice_bytes(long long w, long long value_bytes) {
-    return ((w + 1) / 2) * 1024 + w * S8_ROWS * value_bytes;
+    return ((w + 1) / 2) * 1024 + w * SLICE_ROWS * value_bytes;
 }
 
-template <typename V> struct vec2;
-template <> struct vec2<double> { typedef double2v type; };
-template <> struct vec2<float> { typedef float2v type; };
 template <typename V> struct bits_of;
 template <> struct bits_of<double> { typedef unsigned long long type; };
 template <> struct bits_of<float> { typedef unsigned type; };
@@ -78,7 +69,7 @@ void sell8_kernel(long long n, long long nslices, V alpha, int append, int ell_w
     const long long s = traversal_block(trav, nslices);
     if (s < 0) return;
     const int t = threadIdx.x;
-    const long long i = s * S8_ROWS + 2 * t;
+    const long long i = s * SLICE_ROWS + 2 * t;
     const int w = W > 0 ? W : ell_w;
     const int wp = (w + 1) / 2;
     const char *slice = buf + s * slice_bytes(w, sizeof(V));
@@ -94,39 +85,32 @@ void sell8_kernel(long long n, long long nslices, V alpha, int append, int ell_w
 #pragma unroll
         for (int jp = 0; jp < WP; ++jp) c[jp] = __builtin_nontemporal_load(cw + jp * 256);
 #pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * S8_ROWS));
+        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
         V xv[W][2];
 #pragma unroll
         for (int j = 0; j < W; ++j)
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const unsigned code = (c[j >> 1] >> (8 * ((j & 1) * 2 + q))) & 255u;
-                xv[j][q] = (code < S8_FIRST_PAD) ? x[i + q + s_delta[code]] : V(0);
+                const unsigned code = code_of(c, j, q);
+                xv[j][q] = (code < PAD_UNSAFE) ? x[i + q + s_delta[code]] : V(0);
             }
 #pragma unroll
         for (int j = 0; j < W; ++j)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const unsigned code = (c[j >> 1] >> (8 * ((j & 1) * 2 + q))) & 255u;
-                if (code < S8_FIRST_PAD) sum[q] += v[j][q] * xv[j][q];
-            }
+            for (int q = 0; q < 2; ++q)
+                if (code_of(c, j, q) < PAD_UNSAFE) sum[q] += v[j][q] * xv[j][q];
     } else {
         for (int j = 0; j < w; ++j) {
             const unsigned cword = cw[(j >> 1) * 256];
-            const V2 vv = *reinterpret_cast<const V2 *>(vp + (long long)j * S8_ROWS);
+            const V2 vv = *reinterpret_cast<const V2 *>(vp + (long long)j * SLICE_ROWS);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const unsigned code = (cword >> (8 * ((j & 1) * 2 + q))) & 255u;
-                if (code < S8_FIRST_PAD) sum[q] += vv[q] * x[i + q + s_delta[code]];
+                const unsigned code = code_of(cword, j, q);
+                if (code < PAD_UNSAFE) sum[q] += vv[q] * x[i + q + s_delta[code]];
             }
         }
     }
-    if (csr_ptr) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (i + q < n)
-                for (int j = csr_ptr[i + q], e = csr_ptr[i + q + 1]; j < e; ++j) sum[q] += csr_val[j] * x[csr_col[j]];
-    }
+    add_csr_tail<V>(n, i, csr_ptr, csr_col, csr_val, &x, &sum);
     store_pair<V>(n, i, alpha, append, sum, y, trav);
 }
 
@@ -331,19 +315,19 @@ __device__ __forceinline__ int table_find(const T *s_table, int count, T key) {
     return (lo < count && s_table[lo] == key) ? lo : -1;
 }
 
-// code of a diagonal, S8_PAD if it is not in the table
+// code of a diagonal, PAD if it is not in the table
 __device__ __forceinline__ unsigned delta_code(const int *s_table, int ndeltas, long long dl) {
-    if (dl < INT_MIN || dl > INT_MAX) return S8_PAD;
+    if (dl < INT_MIN || dl > INT_MAX) return PAD;
     const int p = table_find(s_table, ndeltas, (int)dl);
-    return p >= 0 ? (unsigned)p : S8_PAD;
+    return p >= 0 ? (unsigned)p : PAD;
 }
 
 // padding code of the empty half of a column whose other half holds column index `c` of row half `q`:
 // 255 when the 16-byte load of the pair kernels (x[c - q], x[c - q + 1]) stays inside x, 254 otherwise
 __device__ __forceinline__ unsigned pad_code(int partner_col, int partner_q, int max_col) {
-    if (partner_col < 0) return S8_PAD;                                 // both halves empty
+    if (partner_col < 0) return PAD;                                 // both halves empty
     const long long first = (long long)partner_col - partner_q;        // element the 16-byte load starts at
-    return (first >= 0 && first + 1 <= max_col) ? S8_PAD : S8_PAD_UNSAFE;
+    return (first >= 0 && first + 1 <= max_col) ? PAD : PAD_UNSAFE;
 }
 
 // One LDS counter bump per entry -- but the lanes of a wave that walk the rows of one stencil hold the SAME code in the same
@@ -377,7 +361,7 @@ template <typename V> struct stored_values {
     static __device__ __forceinline__ entry direct(V v) { return v; }
     static __device__ __forceinline__ entry none() { return V(0); }
     __device__ __forceinline__ void begin_slice(char *slice, int wp, int t) { vp = reinterpret_cast<V *>(slice + (long long)wp * 1024) + 2 * t; }
-    __device__ __forceinline__ void emit(int j, bool inside, int q, bool, entry e, int *) const { if (inside) vp[(long long)j * S8_ROWS + q] = e; }
+    __device__ __forceinline__ void emit(int j, bool inside, int q, bool, entry e, int *) const { if (inside) vp[(long long)j * SLICE_ROWS + q] = e; }
 };
 
 // SELL8V: a word of value codes next to every word of diagonal codes, 255 for padding (table entry 255 = 0.0).  This storage
@@ -466,15 +450,15 @@ void coded_fill_kernel(Store st, long long n, long long nslices, int w, int ndel
     const int max_col = *max_col_p;
     const int wp = (w + 1) / 2;
     // one lane per row PAIR (the unit the product kernel reads)
-    for (long long pr = (long long)blockIdx.x * blockDim.x + threadIdx.x; pr < nslices * (S8_ROWS / 2);
+    for (long long pr = (long long)blockIdx.x * blockDim.x + threadIdx.x; pr < nslices * (SLICE_ROWS / 2);
          pr += (long long)gridDim.x * blockDim.x) {
-        const long long s = pr / (S8_ROWS / 2);
-        const int t = (int)(pr % (S8_ROWS / 2));
+        const long long s = pr / (SLICE_ROWS / 2);
+        const int t = (int)(pr % (SLICE_ROWS / 2));
         char *slice = buf + s * Store::slice_stride(w);
         unsigned *cw = reinterpret_cast<unsigned *>(slice) + t;
         st.begin_slice(slice, wp, t);
         long long b[2] = {0, 0}, e[2] = {0, 0};
-        const long long i = s * S8_ROWS + 2 * t;
+        const long long i = s * SLICE_ROWS + 2 * t;
         for (int q = 0; q < 2; ++q) if (i + q < n) { b[q] = ptr[i + q]; e[q] = ptr[i + q + 1]; }
         const int n0 = (int)min(e[0] - b[0], (long long)w), n1 = (int)min(e[1] - b[1], (long long)w);
         pair_walk pw;
@@ -519,7 +503,7 @@ void coded_fill_kernel(Store st, long long n, long long nslices, int w, int ndel
                     if (has[q]) {
                         if (q == 1 && has[0] && ec[1] == ec[0] + 1) code = (word >> (8 * (jj * 2))) & 255u;     // the partner's diagonal: its code
                         else code = delta_code(s_table, ndeltas, (long long)ec[q] - (i + q));
-                        if (code != S8_PAD) count_code(s_cnt, code); else atomicExch(&info[1], 1);
+                        if (code != PAD) count_code(s_cnt, code); else atomicExch(&info[1], 1);
                     } else code = pad_code(has[1 - q] ? ec[1 - q] : -1, 1 - q, max_col);
                     word |= code << (8 * (jj * 2 + q));
                     st.emit(j, j < w, q, has[q], ev[q], info);
@@ -560,7 +544,7 @@ void sell8v_kernel(long long n, long long nslices, V alpha, int append, int ell_
     const long long s = traversal_block(trav, nslices);
     if (s < 0) return;
     const int t = threadIdx.x;
-    const long long i = s * S8_ROWS + 2 * t;
+    const long long i = s * SLICE_ROWS + 2 * t;
     const int w = W > 0 ? W : ell_w;
     const int wp = (w + 1) / 2;
     const long long sb = blocks ? (long long)blocks[s] : s;                 // slice dictionary (below): where slice s is stored
@@ -578,17 +562,14 @@ void sell8v_kernel(long long n, long long nslices, V alpha, int append, int ell_
         for (int j = 0; j < W; ++j)
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const unsigned code = (c[j >> 1] >> (8 * ((j & 1) * 2 + q))) & 255u;
-                xv[j][q] = (code < S8_FIRST_PAD) ? x[i + q + s_delta[code]] : V(0);
+                const unsigned code = code_of(c, j, q);
+                xv[j][q] = (code < PAD_UNSAFE) ? x[i + q + s_delta[code]] : V(0);
             }
 #pragma unroll
         for (int j = 0; j < W; ++j)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int sh = 8 * ((j & 1) * 2 + q);
-                const unsigned code = (c[j >> 1] >> sh) & 255u;
-                if (code < S8_FIRST_PAD) sum[q] += s_value[(vc[j >> 1] >> sh) & 255u] * xv[j][q];
-            }
+            for (int q = 0; q < 2; ++q)
+                if (code_of(c, j, q) < PAD_UNSAFE) sum[q] += s_value[code_of(vc, j, q)] * xv[j][q];
     } else {
         // any width (round 6: eight columns per trip -- their four code words, then their sixteen elements of x, are requested before the
         // first product; with one column per trip a 27-point row waited for memory 27 times: 0.60 -> see profiles/r06_widen_probe_unrolled.json).
@@ -603,34 +584,25 @@ void sell8v_kernel(long long n, long long nslices, V alpha, int append, int ell_
             for (int u = 0; u < 8; ++u)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const unsigned code = (c[u >> 1] >> (8 * ((u & 1) * 2 + q))) & 255u;
-                    xv[u][q] = (code < S8_FIRST_PAD) ? x[i + q + s_delta[code]] : V(0);
+                    const unsigned code = code_of(c, u, q);
+                    xv[u][q] = (code < PAD_UNSAFE) ? x[i + q + s_delta[code]] : V(0);
                 }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int sh = 8 * ((u & 1) * 2 + q);
-                    const unsigned code = (c[u >> 1] >> sh) & 255u;
-                    if (code < S8_FIRST_PAD) sum[q] += s_value[(vc[u >> 1] >> sh) & 255u] * xv[u][q];
-                }
+                for (int q = 0; q < 2; ++q)
+                    if (code_of(c, u, q) < PAD_UNSAFE) sum[q] += s_value[code_of(vc, u, q)] * xv[u][q];
         }
         for (; j < w; ++j) {
             const unsigned cword = cw[(j >> 1) * 256], vword = vw[(j >> 1) * 256];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const int sh = 8 * ((j & 1) * 2 + q);
-                const unsigned code = (cword >> sh) & 255u;
-                if (code < S8_FIRST_PAD) sum[q] += s_value[(vword >> sh) & 255u] * x[i + q + s_delta[code]];
+                const unsigned code = code_of(cword, j, q);
+                if (code < PAD_UNSAFE) sum[q] += s_value[code_of(vword, j, q)] * x[i + q + s_delta[code]];
             }
         }
     }
-    if (csr_ptr) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (i + q < n)
-                for (int j = csr_ptr[i + q], e = csr_ptr[i + q + 1]; j < e; ++j) sum[q] += csr_val[j] * x[csr_col[j]];
-    }
+    add_csr_tail<V>(n, i, csr_ptr, csr_col, csr_val, &x, &sum);
     store_pair<V>(n, i, alpha, append, sum, y, trav);
 }
 
@@ -677,7 +649,7 @@ void sell8v_runs_plan_kernel(const char *__restrict__ pool, int w, const int *__
             if (j < w) {
                 const unsigned word = cw[(j >> 1) * 256] >> (16 * (j & 1)), vword = vw[(j >> 1) * 256] >> (16 * (j & 1));
                 const unsigned c0 = word & 255u, c1 = (word >> 8) & 255u, v0 = vword & 255u, v1 = (vword >> 8) & 255u;
-                const bool e0 = c0 < S8_FIRST_PAD, e1 = c1 < S8_FIRST_PAD;
+                const bool e0 = c0 < PAD_UNSAFE, e1 = c1 < PAD_UNSAFE;
                 m0 = __builtin_amdgcn_ballot_w64(e0); m1 = __builtin_amdgcn_ballot_w64(e1);
                 const unsigned long long any = m0 | m1;
                 if (any) {
@@ -746,8 +718,8 @@ void sell8v_runs_kernel(long long n, long long nslices, V alpha, int append, int
     }
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const long long i = s * S8_ROWS + 2 * t;
-    const long long r_lo = s * S8_ROWS + 128 * wave, r_hi = r_lo + 127;         // the wave's rows
+    const long long i = s * SLICE_ROWS + 2 * t;
+    const long long r_lo = s * SLICE_ROWS + 128 * wave, r_hi = r_lo + 127;         // the wave's rows
     const int wp = (w + 1) / 2;
     const long long sb = (long long)__builtin_amdgcn_readfirstlane(blocks[s]);
     const unsigned *cw = reinterpret_cast<const unsigned *>(pool + sb * ((long long)wp * 2048)) + t;
@@ -798,8 +770,8 @@ void sell8v_runs_kernel(long long n, long long nslices, V alpha, int append, int
                 const int sh = 16 * (j & 1);
                 const unsigned cword = cw[(j >> 1) * 256], vword = vw[(j >> 1) * 256];
                 const unsigned c0 = (cword >> sh) & 255u, c1 = (cword >> (sh + 8)) & 255u;
-                if (c0 < S8_FIRST_PAD) sum[0] += s_value[(vword >> sh) & 255u] * x[i + s_delta[c0]];
-                if (c1 < S8_FIRST_PAD) sum[1] += s_value[(vword >> (sh + 8)) & 255u] * x[i + 1 + s_delta[c1]];
+                if (c0 < PAD_UNSAFE) sum[0] += s_value[(vword >> sh) & 255u] * x[i + s_delta[c0]];
+                if (c1 < PAD_UNSAFE) sum[1] += s_value[(vword >> (sh + 8)) & 255u] * x[i + 1 + s_delta[c1]];
             }
         }
     }
@@ -857,7 +829,7 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
         const V *__restrict__ x, V *__restrict__ y, trav_dev trav, const char *__restrict__ pool, const int *__restrict__ blocks)
 {
     constexpr int WP = (W + 1) / 2;
-    constexpr long long SLICE = VCODED ? (long long)WP * 2048 : ((long long)WP * 1024 + (long long)W * S8_ROWS * (long long)sizeof(V));
+    constexpr long long SLICE = VCODED ? (long long)WP * 2048 : ((long long)WP * 1024 + (long long)W * SLICE_ROWS * (long long)sizeof(V));
     typedef typename vec2<V>::type V2;
     __shared__ int s_delta[256];
     __shared__ V s_value[VCODED ? 256 : 1];
@@ -873,7 +845,7 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
     const long long s = traversal_block(trav, nslices);
     const long long sl = s < 0 ? 0 : s;                       // holes of the strip order: load slice 0, store nothing
     const int t = threadIdx.x;
-    const long long i = sl * S8_ROWS + 2 * t;
+    const long long i = sl * SLICE_ROWS + 2 * t;
     // DICT (slice dictionary, below): the CODES of slice s are block blocks[s] of a small pool of distinct code blocks; the
     // pool lives in L1 / L2, so its loads are plain (cached) ones -- streamed codes keep their non-temporal loads.  Stored
     // values (VCODED = false) stay in the slice.
@@ -882,19 +854,14 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
     unsigned c[WP], vc[VCODED ? WP : 1];
 #pragma unroll
     for (int jp = 0; jp < WP; ++jp) {
-        if constexpr (DICT) {
-            c[jp] = cw[jp * 256];
-            if constexpr (VCODED) vc[jp] = cw[(WP + jp) * 256];
-        } else {
-            c[jp] = __builtin_nontemporal_load(cw + jp * 256);
-            if constexpr (VCODED) vc[jp] = __builtin_nontemporal_load(cw + (WP + jp) * 256);
-        }
+        c[jp] = load_code<DICT>(cw + jp * 256);
+        if constexpr (VCODED) vc[jp] = load_code<DICT>(cw + (WP + jp) * 256);
     }
     V2 v[VCODED ? 1 : W];
     if constexpr (!VCODED) {
         const V *vp = reinterpret_cast<const V *>(buf + sl * SLICE + (long long)WP * 1024) + 2 * t;
 #pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * S8_ROWS));
+        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
     }
     s_delta[threadIdx.x] = deltas[threadIdx.x];
     if constexpr (VCODED) s_value[threadIdx.x] = values[threadIdx.x];
@@ -904,48 +871,25 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
     int d[W];
 #pragma unroll
     for (int j = 0; j < W; ++j) {
-        const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-        d[j] = s_delta[c0 < S8_PAD_UNSAFE ? c0 : c1];
+        const unsigned c0 = code_of(c, j, 0), c1 = code_of(c, j, 1);
+        d[j] = s_delta[c0 < PAD_UNSAFE ? c0 : c1];
     }
+    // the 16-byte load is skipped only when NO lane of the wave has a pair in a column (matrices without band structure);
+    // lanes without one read the diagonal table instead
     V xv[W][2];
 #pragma unroll
-    for (int j = 0; j < W; ++j) {
-        const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-        const bool m0 = c0 < S8_PAD_UNSAFE, m1 = c1 < S8_PAD_UNSAFE;
-        const bool pair = (c0 == c1) || (c0 == S8_PAD && m1) || (c1 == S8_PAD && m0);
-        // the 16-byte load is skipped only when NO lane of the wave has a pair in this column (matrices without
-        // band structure); lanes without one read the diagonal table instead
-        const bool use16 = pair && (m0 || m1);
-        V2 p = {V(0), V(0)};
-        if (__builtin_amdgcn_ballot_w64(use16) != 0) {
-            const V *px = use16 ? x + (i + d[j]) : reinterpret_cast<const V *>(deltas);
-            __builtin_memcpy(&p, px, sizeof(V2));
-        }
-        xv[j][0] = p.x; xv[j][1] = p.y;
-        if (!pair) {                       // different diagonals in one lane, or a 16-byte load that would leave x
-            if (m0) xv[j][0] = x[i + s_delta[c0]];
-            if (m1) xv[j][1] = x[i + 1 + s_delta[c1]];
-        }
-        xv[j][0] = m0 ? xv[j][0] : V(0);
-        xv[j][1] = m1 ? xv[j][1] : V(0);
-    }
+    for (int j = 0; j < W; ++j) gather_pair<V>(x, i, code_of(c, j, 0), code_of(c, j, 1), d[j], s_delta, deltas, xv[j][0], xv[j][1]);
     V sum[2] = {V(0), V(0)};
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            const int sh = 16 * (j & 1) + 8 * q;
             V a;
-            if constexpr (VCODED) a = s_value[((c[j >> 1] >> sh) & 255u) < S8_PAD_UNSAFE ? (vc[j >> 1] >> sh) & 255u : 255u];   // entry 255 is 0.0
-            else a = v[j][q];                                                                                              // stored as 0 for padding
+            if constexpr (VCODED) a = s_value[code_of(c, j, q) < PAD_UNSAFE ? code_of(vc, j, q) : 255u];   // entry 255 is 0.0
+            else a = v[j][q];                                                                          // stored as 0 for padding
             sum[q] += a * xv[j][q];
         }
-    if (csr_ptr) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (i + q < n)
-                for (int j = csr_ptr[i + q], e = csr_ptr[i + q + 1]; j < e; ++j) sum[q] += csr_val[j] * x[csr_col[j]];
-    }
+    add_csr_tail<V>(n, i, csr_ptr, csr_col, csr_val, &x, &sum);
     store_pair<V>(n, i, alpha, append, sum, y, trav);
 }
 
@@ -964,7 +908,7 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
         const V *__restrict__ x, V *__restrict__ y, const char *__restrict__ pool, const int *__restrict__ blocks, halo_dev H)
 {
     constexpr int WP = (W + 1) / 2;
-    constexpr long long SLICE = VCODED ? (long long)WP * 2048 : ((long long)WP * 1024 + (long long)W * S8_ROWS * (long long)sizeof(V));
+    constexpr long long SLICE = VCODED ? (long long)WP * 2048 : ((long long)WP * 1024 + (long long)W * SLICE_ROWS * (long long)sizeof(V));
     constexpr long long CODE_BYTES = VCODED ? (long long)WP * 2048 : (long long)WP * 1024;
     typedef typename vec2<V>::type V2;
     __shared__ int s_delta[256];
@@ -974,8 +918,8 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     // own slices [0, ns); the first / last `edge` of them reach into a ghost range.  Dispatch order: the inner ones, then the lower
     // edge, then the upper edge (a workgroup that waits for a flag holds its CU slot: it must not start before the ones that do not)
     const long long hlo = (long long)H.z0 * H.halo;                       // rows of the lower ghost range (0: no neighbour below)
-    const long long ns = (own_rows + S8_ROWS - 1) / S8_ROWS;
-    const long long edge = ((long long)H.lo_planes + S8_ROWS - 1) / S8_ROWS;      // H.lo_planes: the reach of the diagonals in rows (comm.hip)
+    const long long ns = (own_rows + SLICE_ROWS - 1) / SLICE_ROWS;
+    const long long edge = ((long long)H.lo_planes + SLICE_ROWS - 1) / SLICE_ROWS;      // H.lo_planes: the reach of the diagonals in rows (comm.hip)
     const long long elo = H.lo ? (edge < ns ? edge : ns) : 0, ehi = H.hi ? (edge < ns - elo ? edge : ns - elo) : 0;
     const long long inner = ns - elo - ehi;
     long long so = blockIdx.x;                                            // -> own slice
@@ -992,20 +936,20 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     const unsigned n_counted = (unsigned)(elo + ehi) + (inner > 0 ? 1u : 0u);
     const unsigned long long step = counted ? *H.step : 0ull;
     halo_announce(H, step);
-    const long long sl = so + hlo / S8_ROWS;                              // slice of the stored strip
-    const long long i = sl * S8_ROWS + 2 * t;                             // row, stored numbering
+    const long long sl = so + hlo / SLICE_ROWS;                              // slice of the stored strip
+    const long long i = sl * SLICE_ROWS + 2 * t;                             // row, stored numbering
     const unsigned *cw = reinterpret_cast<const unsigned *>(DICT ? pool + (long long)blocks[sl] * CODE_BYTES : buf + sl * SLICE) + t;
     unsigned c[WP], vc[VCODED ? WP : 1];
 #pragma unroll
     for (int jp = 0; jp < WP; ++jp) {
-        if constexpr (DICT) { c[jp] = cw[jp * 256]; if constexpr (VCODED) vc[jp] = cw[(WP + jp) * 256]; }
-        else { c[jp] = __builtin_nontemporal_load(cw + jp * 256); if constexpr (VCODED) vc[jp] = __builtin_nontemporal_load(cw + (WP + jp) * 256); }
+        c[jp] = load_code<DICT>(cw + jp * 256);
+        if constexpr (VCODED) vc[jp] = load_code<DICT>(cw + (WP + jp) * 256);
     }
     V2 v[VCODED ? 1 : W];
     if constexpr (!VCODED) {
         const V *vp = reinterpret_cast<const V *>(buf + sl * SLICE + (long long)WP * 1024) + 2 * t;
 #pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * S8_ROWS));
+        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
     }
     s_delta[t] = deltas[t];
     if constexpr (VCODED) s_value[t] = values[t];
@@ -1014,18 +958,18 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     if (edge_wg) ghosts_ok = halo_wait(H, step, need_lo && H.lo, need_hi && H.hi, &s_flag);
     const V *xe = x - hlo;                                                // x in stored numbering (own range only)
     V xv[W][2];
-    if (!edge_wg) {
+    if (!edge_wg) {             // a copy of gather_pair (slices.hpp) on xe: to move onto it once this kernel has a one-process test
         int d[W];
 #pragma unroll
         for (int j = 0; j < W; ++j) {
             const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            d[j] = s_delta[c0 < S8_PAD_UNSAFE ? c0 : c1];
+            d[j] = s_delta[c0 < PAD_UNSAFE ? c0 : c1];
         }
 #pragma unroll
         for (int j = 0; j < W; ++j) {
             const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            const bool m0 = c0 < S8_PAD_UNSAFE, m1 = c1 < S8_PAD_UNSAFE;
-            const bool pair = (c0 == c1) || (c0 == S8_PAD && m1) || (c1 == S8_PAD && m0);
+            const bool m0 = c0 < PAD_UNSAFE, m1 = c1 < PAD_UNSAFE;
+            const bool pair = (c0 == c1) || (c0 == PAD && m1) || (c1 == PAD && m0);
             const bool use16 = pair && (m0 || m1);
             V2 p = {V(0), V(0)};
             if (__builtin_amdgcn_ballot_w64(use16) != 0) {
@@ -1051,8 +995,8 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
 #pragma unroll
         for (int j = 0; j < W; ++j) {
             const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            xv[j][0] = c0 < S8_PAD_UNSAFE ? at(i + s_delta[c0]) : V(0);
-            xv[j][1] = c1 < S8_PAD_UNSAFE ? at(i + 1 + s_delta[c1]) : V(0);
+            xv[j][0] = c0 < PAD_UNSAFE ? at(i + s_delta[c0]) : V(0);
+            xv[j][1] = c1 < PAD_UNSAFE ? at(i + 1 + s_delta[c1]) : V(0);
         }
     }
     V sum[2] = {V(0), V(0)};
@@ -1062,7 +1006,7 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
         for (int q = 0; q < 2; ++q) {
             const int sh = 16 * (j & 1) + 8 * q;
             V a;
-            if constexpr (VCODED) a = s_value[((c[j >> 1] >> sh) & 255u) < S8_PAD_UNSAFE ? (vc[j >> 1] >> sh) & 255u : 255u];
+            if constexpr (VCODED) a = s_value[((c[j >> 1] >> sh) & 255u) < PAD_UNSAFE ? (vc[j >> 1] >> sh) & 255u : 255u];
             else a = v[j][q];
             sum[q] += a * xv[j][q];
         }
@@ -1179,7 +1123,7 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
     constexpr int WP = (W + 1) / 2;
     constexpr long long CODE_BYTES = (long long)WP * 2048;
     constexpr int VB = (int)sizeof(V);
-    constexpr int SLB = S8_ROWS * VB;                          // bytes of x per slice
+    constexpr int SLB = SLICE_ROWS * VB;                          // bytes of x per slice
     typedef typename vec2<V>::type V2;
     typedef const __attribute__((address_space(4))) march_cold<V> *kernarg_ptr;
     extern __shared__ __align__(16) unsigned char s_march[];  // [ring: cap_b][mirror of its first span_b bytes][far 0: SLB][far 1: SLB][diagonal table: 1 KiB][value table]
@@ -1201,27 +1145,27 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
 
     const int capb = mp.cap_b, spanb = mp.span_b, farb = capb + spanb;
     const int hi2 = mp.lo_e + spanb / VB;                     // the window of a slice: x[i0 + lo_e .. i0 + 512 + hi2)
-    const long long i00 = first * S8_ROWS;
+    const long long i00 = first * SLICE_ROWS;
     const unsigned lane_b = 2u * (unsigned)t * VB;
     // Iteration k requests the 512 elements slice k + 2 adds to the window and the far diagonals of slice k + 1, and stores
     // the rows of slice k.  [kA, kend): the iterations for which all of that lies inside x and y -- the hot loop.
     int kA = 0, kend = count;
     {
         const auto *c = cold();
-        long long m = 2 * S8_ROWS + hi2, M = m;
-        if (mp.nfar > 0) { const long long f = S8_ROWS + (long long)mp.far0; m = f < m ? f : m; M = f > M ? f : M; }
-        if (mp.nfar > 1) { const long long f = S8_ROWS + (long long)mp.far1; m = f < m ? f : m; M = f > M ? f : M; }
+        long long m = 2 * SLICE_ROWS + hi2, M = m;
+        if (mp.nfar > 0) { const long long f = SLICE_ROWS + (long long)mp.far0; m = f < m ? f : m; M = f > M ? f : M; }
+        if (mp.nfar > 1) { const long long f = SLICE_ROWS + (long long)mp.far1; m = f < m ? f : m; M = f > M ? f : M; }
         const long long a = -(i00 + m);
-        if (a > 0) { const long long q = (a + S8_ROWS - 1) / S8_ROWS; kA = q > count ? count : (int)q; }
-        const long long bb = mp.x_last - (S8_ROWS - 1) - M - i00;
-        const long long kB = bb >= 0 ? bb / S8_ROWS + 1 : 0;
-        const long long kS = c->n / S8_ROWS - first;
+        if (a > 0) { const long long q = (a + SLICE_ROWS - 1) / SLICE_ROWS; kA = q > count ? count : (int)q; }
+        const long long bb = mp.x_last - (SLICE_ROWS - 1) - M - i00;
+        const long long kB = bb >= 0 ? bb / SLICE_ROWS + 1 : 0;
+        const long long kS = c->n / SLICE_ROWS - first;
         if (kB < kend) kend = (int)kB;
         if (kS < kend) kend = kS > 0 ? (int)kS : 0;
         if (c->csr_ptr || (reinterpret_cast<unsigned long long>(y) & (2 * VB - 1)) != 0) kend = 0;
     }
     auto load512 = [&](long long gb) -> V2 {
-        if (gb >= 0 && gb + S8_ROWS - 1 <= mp.x_last) { V2 v; __builtin_memcpy(&v, x + gb + 2 * t, sizeof(V2)); return v; }
+        if (gb >= 0 && gb + SLICE_ROWS - 1 <= mp.x_last) { V2 v; __builtin_memcpy(&v, x + gb + 2 * t, sizeof(V2)); return v; }
         return load_pair_clamped<V>(x, gb + 2 * t, mp.x_last);
     };
     // The prologue of a run costs round trips, not bytes (the first build: three for the window, one for the registers, three
@@ -1245,19 +1189,19 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
         const int wpairs = (SLB + spanb) / (2 * VB);
         V2 w[4];
         const long long glo = g0 < i00 + mp.far0 ? g0 : i00 + mp.far0;
-        long long ghi = i00 + 2 * S8_ROWS + hi2;                     // one past the last element any of these loads touches
-        if (mp.nfar > 0 && i00 + S8_ROWS + mp.far0 > ghi) ghi = i00 + S8_ROWS + mp.far0;
-        if (mp.nfar > 1 && i00 + S8_ROWS + mp.far1 > ghi) ghi = i00 + S8_ROWS + mp.far1;
+        long long ghi = i00 + 2 * SLICE_ROWS + hi2;                     // one past the last element any of these loads touches
+        if (mp.nfar > 0 && i00 + SLICE_ROWS + mp.far0 > ghi) ghi = i00 + SLICE_ROWS + mp.far0;
+        if (mp.nfar > 1 && i00 + SLICE_ROWS + mp.far1 > ghi) ghi = i00 + SLICE_ROWS + mp.far1;
         if (glo >= 0 && (mp.nfar < 2 || i00 + mp.far1 >= 0) && ghi - 1 <= mp.x_last) {      // uniform: nothing to clamp
 #pragma unroll
             for (int u = 0; u < 4; ++u) { w[u] = V2{V(0), V(0)}; if (t + u * 256 < wpairs) __builtin_memcpy(&w[u], x + g0 + 2 * (t + u * 256), sizeof(V2)); }
-            __builtin_memcpy(&chunk, x + i00 + S8_ROWS + hi2 + 2 * t, sizeof(V2));
+            __builtin_memcpy(&chunk, x + i00 + SLICE_ROWS + hi2 + 2 * t, sizeof(V2));
             if (mp.nfar > 0) __builtin_memcpy(&f0, x + i00 + mp.far0 + 2 * t, sizeof(V2));
             if (mp.nfar > 1) __builtin_memcpy(&f1, x + i00 + mp.far1 + 2 * t, sizeof(V2));
         } else {
 #pragma unroll
             for (int u = 0; u < 4; ++u) { w[u] = V2{V(0), V(0)}; if (t + u * 256 < wpairs) w[u] = load_pair_clamped<V>(x, g0 + 2 * (t + u * 256), mp.x_last); }
-            if (count > 1) chunk = load512(i00 + S8_ROWS + hi2);
+            if (count > 1) chunk = load512(i00 + SLICE_ROWS + hi2);
             if (mp.nfar > 0) f0 = load512(i00 + mp.far0);
             if (mp.nfar > 1) f1 = load512(i00 + mp.far1);
         }
@@ -1279,8 +1223,8 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
         for (int j = 0; j < W; ++j) {
             const unsigned cword = cwv[j >> 1] >> (16 * (j & 1)), vword = cwv[WP + (j >> 1)] >> (16 * (j & 1));
             const unsigned c0 = cword & 255u, c1 = (cword >> 8) & 255u;
-            const bool m0 = c0 < S8_PAD_UNSAFE, m1 = c1 < S8_PAD_UNSAFE, any = m0 || m1;
-            const bool pair = (c0 == c1) || (c0 == S8_PAD && m1) || (c1 == S8_PAD && m0);
+            const bool m0 = c0 < PAD_UNSAFE, m1 = c1 < PAD_UNSAFE, any = m0 || m1;
+            const bool pair = (c0 == c1) || (c0 == PAD && m1) || (c1 == PAD && m0);
             const int d = any ? s_delta[m0 ? c0 : c1] : 0;
             // the wave's diagonal in this column: that of its first lane with an entry
             const unsigned long long have = __builtin_amdgcn_ballot_w64(any);
@@ -1332,10 +1276,10 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
     int k = 0;
     auto hot = [&](auto far_tag) {
         constexpr bool FAR = decltype(far_tag)::value;
-        const char *xc = reinterpret_cast<const char *>(x + (i00 + (long long)(k + 2) * S8_ROWS + hi2));   // uniform running pointers
-        const char *xf0 = reinterpret_cast<const char *>(x + (i00 + (long long)(k + 1) * S8_ROWS + mp.far0));
-        const char *xf1 = reinterpret_cast<const char *>(x + (i00 + (long long)(k + 1) * S8_ROWS + (mp.nfar > 1 ? mp.far1 : mp.far0)));
-        char *ys = reinterpret_cast<char *>(y + (i00 + (long long)k * S8_ROWS));
+        const char *xc = reinterpret_cast<const char *>(x + (i00 + (long long)(k + 2) * SLICE_ROWS + hi2));   // uniform running pointers
+        const char *xf0 = reinterpret_cast<const char *>(x + (i00 + (long long)(k + 1) * SLICE_ROWS + mp.far0));
+        const char *xf1 = reinterpret_cast<const char *>(x + (i00 + (long long)(k + 1) * SLICE_ROWS + (mp.nfar > 1 ? mp.far1 : mp.far0)));
+        char *ys = reinterpret_cast<char *>(y + (i00 + (long long)k * SLICE_ROWS));
         // how many of the next slices keep this code block: one look at blocks[] per entry, no scalar load inside the loop
         // (a scalar load in flight turns every partial wait for the LDS reads into a full one)
         int kstop;
@@ -1380,12 +1324,12 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
         }
         // ---- a general slice: clamped loads, rows checked against n, the code block decoded if it is a new one ----
         const auto *c = cold();
-        const long long i0 = i00 + (long long)k * S8_ROWS;
+        const long long i0 = i00 + (long long)k * SLICE_ROWS;
         park(mp.nfar > 0, chunk, f0, f1);
-        if (k + 2 < count) chunk = load512(i0 + 2 * S8_ROWS + hi2);
+        if (k + 2 < count) chunk = load512(i0 + 2 * SLICE_ROWS + hi2);
         if (k + 1 < count) {
-            if (mp.nfar > 0) f0 = load512(i0 + S8_ROWS + mp.far0);
-            if (mp.nfar > 1) f1 = load512(i0 + S8_ROWS + mp.far1);
+            if (mp.nfar > 0) f0 = load512(i0 + SLICE_ROWS + mp.far0);
+            if (mp.nfar > 1) f1 = load512(i0 + SLICE_ROWS + mp.far1);
         }
         const int blk = blocks[first + k];
         const char *pool = c->pool;
@@ -1407,7 +1351,7 @@ void sell8_march_kernel(march_cold<V> cold_args /* first: offset 0 of the kernar
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const unsigned code = (cword >> (8 * q)) & 255u;
-                    if (code < S8_PAD_UNSAFE) sum[q] += s_value[(vword >> (8 * q)) & 255u] * x[i + q + s_delta[code]];
+                    if (code < PAD_UNSAFE) sum[q] += s_value[(vword >> (8 * q)) & 255u] * x[i + q + s_delta[code]];
                 }
             }
         }
@@ -1453,12 +1397,12 @@ void csr_delta_count_kernel(long long n, int w, int ndeltas, const P *__restrict
 
 /// LDS of the march product: ring (span + 2 slices) + mirror (span) + one slice per far diagonal.
 inline long long march_span_bytes(int lo, int hi, int value_bytes) {
-    const long long slb = (long long)S8_ROWS * value_bytes;
+    const long long slb = (long long)SLICE_ROWS * value_bytes;
     const long long lo_e = (long long)lo & ~1ll, hi_e = ((long long)hi + 1) & ~1ll;
     return ((hi_e - lo_e) * value_bytes + slb - 1) / slb * slb;
 }
 inline long long march_lds_bytes(int lo, int hi, int value_bytes) {
-    const long long slb = (long long)S8_ROWS * value_bytes;
+    const long long slb = (long long)SLICE_ROWS * value_bytes;
     return 2 * march_span_bytes(lo, hi, value_bytes) + 4 * slb + 1024 + 256 * value_bytes;      // ring + mirror, two far slots, diagonal and value tables
 }
 
@@ -1481,7 +1425,7 @@ int march_launch(int dev, hipStream_t s, int64_t n, long long ns, V alpha, int a
     VEXHIP_REQUIRE(lds <= 64 * 1024, "bad march plan: window too large");
     static const long long lds_floor = [] { const char *e = env(ENV_VEXHIP_MARCH_LDS); return e ? std::atoll(e) : 0ll; }();   // experiments: fewer workgroups per CU
     if (lds_floor > lds && lds_floor <= 64 * 1024) lds = lds_floor;
-    const march_dev mp = {m->lo, m->hi, lo_e, (int)span_b, (int)(span_b + 2 * S8_ROWS * (long long)sizeof(V)), m->run, m->nfar, m->far[0], m->far[1], (long long)m->x_last};
+    const march_dev mp = {m->lo, m->hi, lo_e, (int)span_b, (int)(span_b + 2 * SLICE_ROWS * (long long)sizeof(V)), m->run, m->nfar, m->far[0], m->far[1], (long long)m->x_last};
     const march_cold<V> cold = {(long long)n, ns, deltas, values, cp, cc, cv, pool, t8};
     bool covered = true;
     with_width<8>(w, [&](auto W) {
@@ -1499,10 +1443,10 @@ template <typename V>
 int sell8_apply_halo_impl(int dev, hipStream_t s, long long own_rows, V alpha, int append, int w, bool vcoded, const void *buf, const void *pool_,
         const int *blocks, const int *deltas, const V *values, const V *x, V *y, halo_dev H)
 {
-    VEXHIP_REQUIRE(H.pull && own_rows > 0 && own_rows % S8_ROWS == 0 && H.halo % S8_ROWS == 0 && w >= 1 && w <= 8, "the one-launch step of a matrix with diagonal codes: whole slices, ELL width <= 8");
+    VEXHIP_REQUIRE(H.pull && own_rows > 0 && own_rows % SLICE_ROWS == 0 && H.halo % SLICE_ROWS == 0 && w >= 1 && w <= 8, "the one-launch step of a matrix with diagonal codes: whole slices, ELL width <= 8");
     VEXHIP_REQUIRE(deltas && x && y && (buf || pool_) && (!vcoded || values), "NULL argument");
     VEXHIP_SET_DEVICE(dev);
-    const long long grid = own_rows / S8_ROWS;
+    const long long grid = own_rows / SLICE_ROWS;
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
     const char *b = static_cast<const char *>(buf), *pool = static_cast<const char *>(pool_);
     with_width<8>(w, [&](auto W) {
@@ -1520,7 +1464,7 @@ inline int grid_for(int dev, int64_t n) {
 
 // Strip traversal from the diagonals every second row (or more) uses: see vexhip.h vexhip_traversal.
 void strip_traversal(int64_t n, const std::vector<int> &table, const std::vector<unsigned long long> &counts,
-        vexhip_traversal *out, int64_t rpb = S8_ROWS)
+        vexhip_traversal *out, int64_t rpb = SLICE_ROWS)
 {
     std::memset(out, 0, sizeof(*out));
     const int64_t tile_rows_max = 65536;
@@ -1530,7 +1474,7 @@ void strip_traversal(int64_t n, const std::vector<int> &table, const std::vector
         if (counts[k] * 2 >= (unsigned long long)n) s_big = std::max<int64_t>(s_big, table[k] < 0 ? -(int64_t)table[k] : table[k]);
     if (s_big < 2 * tile_rows_max || (s_big % rpb) != 0) return;
     const int64_t plane_blocks = s_big / rpb, nb = (n + rpb - 1) / rpb;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(64 * S8_ROWS / rpb, plane_blocks / 8));   // 32 Ki rows per XCD strip
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(64 * SLICE_ROWS / rpb, plane_blocks / 8));   // 32 Ki rows per XCD strip
     const int64_t planes = (nb + plane_blocks - 1) / plane_blocks;
     const int64_t tiles = (plane_blocks + 8 * chunk - 1) / (8 * chunk);
     out->grid_blocks = tiles * planes * 8 * chunk;
@@ -1546,7 +1490,7 @@ int coded_fill(int dev, hipStream_t s, Store st, int64_t n, const P *ptr, const 
         void *buf, vexhip_traversal *trav, int64_t known_max_col, int64_t *max_col, const char *not_in_table)
 {
     VEXHIP_SET_DEVICE(dev);
-    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
+    const long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
     dev_buf<unsigned long long> dcounts;
     VEXHIP_TRY(dcounts.alloc(256 + 4 * sizeof(int) / sizeof(unsigned long long)));
     int *dinfo = reinterpret_cast<int *>(dcounts.p + 256);
@@ -1560,7 +1504,7 @@ int coded_fill(int dev, hipStream_t s, Store st, int64_t n, const P *ptr, const 
         ell_max_col_kernel<P><<<grid_for(dev, n), 256, 0, s>>>(n, (int)std::min<int64_t>(w, INT_MAX), ptr, col, dinfo + 2);
     }
     with_bool(w <= 8, [&](auto STAGED) {
-        coded_fill_kernel<Store, P, STAGED()><<<grid_for(dev, ns * (S8_ROWS / 2)), 256, 0, s>>>(st, n, ns, (int)w, ndeltas, ptr, col, val, deltas, dinfo + 2,
+        coded_fill_kernel<Store, P, STAGED()><<<grid_for(dev, ns * (SLICE_ROWS / 2)), 256, 0, s>>>(st, n, ns, (int)w, ndeltas, ptr, col, val, deltas, dinfo + 2,
                 static_cast<char *>(buf), dcounts.p, dinfo);
     });
     std::vector<unsigned long long> counts(256);
@@ -1651,7 +1595,7 @@ int spmv_sell8(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
     VEXHIP_REQUIRE((pool_ == nullptr) == (blocks == nullptr), "code pool and slice numbers go together");
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
+    const long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
     long long grid = 0;
     const trav_dev t8 = attach(make_traversal(tr, ns, &grid), add);  // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
@@ -1754,7 +1698,7 @@ int spmv_sell8v(int dev, void *stream, int64_t n, V alpha, int append, int64_t w
     VEXHIP_REQUIRE(buf && deltas && values && x && y && (reinterpret_cast<uintptr_t>(buf) & 15) == 0, "SELL8V buffer must be 16-byte aligned");
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
+    const long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
     long long grid = 0;
     trav_dev t8 = make_traversal(tr, ns, &grid);
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
@@ -1960,7 +1904,7 @@ int sell8v_runs_apply(int dev, void *stream, int64_t n, V alpha, int append, int
     VEXHIP_REQUIRE(x && y, "NULL vector");
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    const long long ns = (n + S8_ROWS - 1) / S8_ROWS;
+    const long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
     long long grid = 0;
     trav_dev t8 = make_traversal(tr, ns, &grid);
     if (!t8.order && t8.chunk == 0) grid = 8 * ((ns + 7) / 8);                        // (the kernel deals the slices to the XCDs itself)
@@ -2031,7 +1975,7 @@ using namespace vexhip;
 extern "C" {
 
 int64_t vexhip_sell8_bytes(int64_t n, int64_t w, int value_bytes) {
-    return (n + S8_ROWS - 1) / S8_ROWS * slice_bytes(w, value_bytes);
+    return (n + SLICE_ROWS - 1) / SLICE_ROWS * slice_bytes(w, value_bytes);
 }
 
 int vexhip_sell8_analyze_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col,
@@ -2040,7 +1984,7 @@ int vexhip_sell8_analyze_i32(int dev, void *stream, int64_t n, const int32_t *pt
 
 int vexhip_spmv_sell8_set_variant(int variant) { g_sell8_variant = variant; return 0; }
 
-int64_t vexhip_sell8v_bytes(int64_t n, int64_t w) { return (n + S8_ROWS - 1) / S8_ROWS * ((w + 1) / 2) * 2048; }
+int64_t vexhip_sell8v_bytes(int64_t n, int64_t w) { return (n + SLICE_ROWS - 1) / SLICE_ROWS * ((w + 1) / 2) * 2048; }
 
 int vexhip_sell8v_analyze_f64_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const double *val, int64_t w, double *values, int *nvalues)
 { return sell8v_analyze<double, int32_t>(dev, stream, n, ptr, val, w, values, nvalues); }
@@ -2112,7 +2056,7 @@ int vexhip_sell8_march_plan(int dev, void *stream, const int32_t *deltas, int nd
     for (int dlt : by_abs) {
         const int nlo = std::min(lo, dlt), nhi = std::max(hi, dlt);
         if ((long long)nhi - nlo > (1 << 20) || march_lds_bytes(nlo, nhi, value_bytes) > 48 * 1024) break;
-        if (march_span_bytes(nlo, nhi, value_bytes) / value_bytes + S8_ROWS > 2048) break;       // the first window: <= 4 pairs per lane
+        if (march_span_bytes(nlo, nhi, value_bytes) / value_bytes + SLICE_ROWS > 2048) break;       // the first window: <= 4 pairs per lane
         lo = nlo; hi = nhi;
     }
     // Slices per workgroup.  The prologue of a run costs about two slices (v8b), so long runs -- but a CU holds four workgroups

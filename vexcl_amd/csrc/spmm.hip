@@ -14,64 +14,23 @@
 #include "traversal.hpp"
 #include "storage.hpp"
 #include "dispatch.hpp"
+#include "slices.hpp"
 
 namespace vexhip {
 namespace {
 
-constexpr int ROWS = 512;
-constexpr unsigned PAD8 = 254;        // codes 254 and 255 are padding (sell8.hip, pair kernels)
 constexpr int MAX_NR = 4;
 
-typedef int    int2v    __attribute__((ext_vector_type(2)));
-typedef double double2v __attribute__((ext_vector_type(2)));
-typedef float  float2v  __attribute__((ext_vector_type(2)));
-template <typename V> struct vec2;
-template <> struct vec2<double> { typedef double2v type; };
-template <> struct vec2<float> { typedef float2v type; };
+typedef int int2v __attribute__((ext_vector_type(2)));
 
 template <typename V> struct rhs_set { const V *x[MAX_NR]; V *y[MAX_NR]; };
-
-// x for the two rows of a lane in ELL column j of a diagonal-coded slice, as the single-vector pair kernels read it
-// (sell8.hip, "PAIR kernels"): ONE 16-byte load when both rows sit on the same diagonal or one of them is padding that
-// allows it (code 255), an 8-byte load per real entry otherwise; padding reads as 0.  c0 / c1: the two rows' codes,
-// d: s_delta[c0 is real ? c0 : c1], looked up once per column by the caller.
-template <typename V>
-__device__ __forceinline__ void gather_pair(const V *__restrict__ x, long long i, unsigned c0, unsigned c1, int d,
-        const int *s_delta, const int *__restrict__ safe, V &x0, V &x1)
-{
-    typedef typename vec2<V>::type V2;
-    const bool m0 = c0 < PAD8, m1 = c1 < PAD8;
-    const bool pair = (c0 == c1) || (c0 == 255u && m1) || (c1 == 255u && m0);
-    const bool use16 = pair && (m0 || m1);
-    V2 p = {V(0), V(0)};
-    if (__builtin_amdgcn_ballot_w64(use16) != 0) {          // skipped only when no lane of the wave has a pair here
-        const V *px = use16 ? x + (i + d) : reinterpret_cast<const V *>(safe);
-        __builtin_memcpy(&p, px, sizeof(V2));
-    }
-    x0 = p.x; x1 = p.y;
-    if (!pair) {
-        if (m0) x0 = x[i + s_delta[c0]];
-        if (m1) x1 = x[i + 1 + s_delta[c1]];
-    }
-    x0 = m0 ? x0 : V(0);
-    x1 = m1 ? x1 : V(0);
-}
 
 template <typename V, int NR>
 __device__ __forceinline__ void tail_and_store(long long n, long long i, V alpha, int append,
         const int *__restrict__ csr_ptr, const int *__restrict__ csr_col, const V *__restrict__ csr_val,
         const rhs_set<V> &io, V (&sum)[NR][2])
 {
-    if (csr_ptr) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (i + q < n)
-                for (int j = csr_ptr[i + q], e = csr_ptr[i + q + 1]; j < e; ++j) {
-                    const int c = csr_col[j]; const V v = csr_val[j];
-#pragma unroll
-                    for (int k = 0; k < NR; ++k) sum[k][q] += v * io.x[k][c];
-                }
-    }
+    add_csr_tail<V, NR>(n, i, csr_ptr, csr_col, csr_val, io.x, sum);
 #pragma unroll
     for (int k = 0; k < NR; ++k)
 #pragma unroll
@@ -83,28 +42,37 @@ __device__ __forceinline__ void tail_and_store(long long n, long long i, V alpha
             }
 }
 
-// ---- SELL8: 1-byte diagonal codes (layout: sell8.hip) -----------------------------------
-template <typename V, int W, int NR>
+// ---- SELL8 and SELL8V: 1-byte diagonal codes; matrix values stored in the slice or (VCODED) as 1-byte value codes (layouts: sell8.hip) ----
+// `values` is unused by the stored-value form, `pool` by the value-coded one, whose whole storage is the pool when it has a dictionary.
+template <typename V, int W, int NR, bool VCODED>
 __global__ __launch_bounds__(256)
-void spmm_sell8_kernel(long long n, long long nslices, V alpha, int append, int ell_w,
-        const char *__restrict__ buf, const int *__restrict__ deltas,
+void spmm_coded_kernel(long long n, long long nslices, V alpha, int append, int ell_w,
+        const char *__restrict__ buf, const int *__restrict__ deltas, const V *__restrict__ values,
         const int *__restrict__ csr_ptr, const int *__restrict__ csr_col, const V *__restrict__ csr_val,
         rhs_set<V> io, trav_dev trav, const char *__restrict__ pool, const int *__restrict__ blocks)
 {
     __shared__ int s_delta[256];
+    __shared__ V s_value[VCODED ? 256 : 1];
     s_delta[threadIdx.x] = deltas[threadIdx.x];
+    if constexpr (VCODED) s_value[threadIdx.x] = values[threadIdx.x];
     __syncthreads();
 
     const long long s = traversal_block(trav, nslices);
     if (s < 0) return;
     const int t = threadIdx.x;
-    const long long i = s * ROWS + 2 * t;
+    const long long i = s * SLICE_ROWS + 2 * t;
     const int w = W > 0 ? W : ell_w;
     const int wp = (w + 1) / 2;
-    const char *slice = buf + s * ((long long)wp * 1024 + (long long)w * ROWS * sizeof(V));
-    // slice dictionary (sell8.hip): codes from the pool of distinct code blocks, values from the slice
-    const unsigned *cw = reinterpret_cast<const unsigned *>(blocks ? pool + (long long)blocks[s] * ((long long)wp * 1024) : slice) + t;
-    const V *vp = reinterpret_cast<const V *>(slice + (long long)wp * 1024) + 2 * t;
+    const long long code_bytes = (long long)wp * (VCODED ? 2048 : 1024);
+    const char *slice = buf + s * (VCODED ? code_bytes : code_bytes + (long long)w * SLICE_ROWS * sizeof(V));
+    // slice dictionary (sell8.hip): the codes of slice s are block blocks[s] of the pool of distinct code blocks; stored values stay in the
+    // slice, a value-coded storage is its pool and arrives as buf
+    const char *codes;
+    if constexpr (VCODED) codes = buf + (blocks ? (long long)blocks[s] : s) * code_bytes;
+    else codes = blocks ? pool + (long long)blocks[s] * code_bytes : slice;
+    const unsigned *cw = reinterpret_cast<const unsigned *>(codes) + t;
+    const V *vp = reinterpret_cast<const V *>(slice + code_bytes) + 2 * t;             // stored values
+    const unsigned *vw = cw + wp * 256;                                                // value codes
     typedef typename vec2<V>::type V2;
 
     V sum[NR][2];
@@ -113,116 +81,55 @@ void spmm_sell8_kernel(long long n, long long nslices, V alpha, int append, int 
 
     if constexpr (W > 0) {
         constexpr int WP = (W + 1) / 2;
-        unsigned c[WP]; V2 v[W];
+        unsigned c[WP], vc[VCODED ? WP : 1];
 #pragma unroll
-        for (int jp = 0; jp < WP; ++jp) c[jp] = blocks ? cw[jp * 256] : __builtin_nontemporal_load(cw + jp * 256);
+        for (int jp = 0; jp < WP; ++jp) {
+            if (blocks) { c[jp] = load_code<true>(cw + jp * 256); if constexpr (VCODED) vc[jp] = load_code<true>(vw + jp * 256); }
+            else { c[jp] = load_code<false>(cw + jp * 256); if constexpr (VCODED) vc[jp] = load_code<false>(vw + jp * 256); }
+        }
+        // the matrix values: the slice's pairs as loaded, or looked up in s_value below
+        V2 v[VCODED ? 1 : W]; V a[VCODED ? W : 1][2];
+        if constexpr (!VCODED) {
 #pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * ROWS));
+            for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
+        }
+        auto value = [&](int j, int q) -> V { if constexpr (VCODED) return a[j][q]; else return v[j][q]; };
         int d[W];
 #pragma unroll
         for (int j = 0; j < W; ++j) {
-            const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            d[j] = s_delta[c0 < PAD8 ? c0 : c1];
+            const unsigned c0 = code_of(c, j, 0), c1 = code_of(c, j, 1);
+            d[j] = s_delta[c0 < PAD_UNSAFE ? c0 : c1];
+            if constexpr (VCODED) {
+                a[j][0] = s_value[c0 < PAD_UNSAFE ? code_of(vc, j, 0) : 255u];          // entry 255 is 0.0
+                a[j][1] = s_value[c1 < PAD_UNSAFE ? code_of(vc, j, 1) : 255u];
+            }
         }
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
             V xv[W][2];
 #pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-                gather_pair<V>(io.x[k], i, c0, c1, d[j], s_delta, deltas, xv[j][0], xv[j][1]);
-            }
-            // padding: stored value 0, gathered value 0 -- sum + (+-0) == sum bit for bit (the sum starts at +0)
+            for (int j = 0; j < W; ++j)
+                gather_pair<V>(io.x[k], i, code_of(c, j, 0), code_of(c, j, 1), d[j], s_delta, deltas, xv[j][0], xv[j][1]);
+            // padding: matrix value 0, gathered value 0 -- sum + (+-0) == sum bit for bit (the sum starts at +0)
 #pragma unroll
             for (int j = 0; j < W; ++j)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) sum[k][q] += v[j][q] * xv[j][q];
+                for (int q = 0; q < 2; ++q) sum[k][q] += value(j, q) * xv[j][q];
         }
     } else {
         for (int j = 0; j < w; ++j) {
             const unsigned cword = cw[(j >> 1) * 256];
-            const V2 vv = *reinterpret_cast<const V2 *>(vp + (long long)j * ROWS);
+            unsigned vword = 0; V2 vv = {V(0), V(0)};
+            if constexpr (VCODED) vword = vw[(j >> 1) * 256];
+            else vv = *reinterpret_cast<const V2 *>(vp + (long long)j * SLICE_ROWS);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const unsigned code = (cword >> (8 * ((j & 1) * 2 + q))) & 255u;
-                if (code < PAD8) {
+                const unsigned code = code_of(cword, j, q);
+                if (code < PAD_UNSAFE) {
                     const long long cidx = i + q + s_delta[code];
-#pragma unroll
-                    for (int k = 0; k < NR; ++k) sum[k][q] += vv[q] * io.x[k][cidx];
-                }
-            }
-        }
-    }
-    tail_and_store<V, NR>(n, i, alpha, append, csr_ptr, csr_col, csr_val, io, sum);
-}
-
-// ---- SELL8V: diagonal codes and value codes (layout: sell8.hip) -----------------------------
-template <typename V, int W, int NR>
-__global__ __launch_bounds__(256)
-void spmm_sell8v_kernel(long long n, long long nslices, V alpha, int append, int ell_w,
-        const char *__restrict__ buf, const int *__restrict__ deltas, const V *__restrict__ values,
-        const int *__restrict__ csr_ptr, const int *__restrict__ csr_col, const V *__restrict__ csr_val,
-        rhs_set<V> io, trav_dev trav, const int *__restrict__ blocks)
-{
-    __shared__ int s_delta[256];
-    __shared__ V s_value[256];
-    s_delta[threadIdx.x] = deltas[threadIdx.x];
-    s_value[threadIdx.x] = values[threadIdx.x];
-    __syncthreads();
-
-    const long long s = traversal_block(trav, nslices);
-    if (s < 0) return;
-    const int t = threadIdx.x;
-    const long long i = s * ROWS + 2 * t;
-    const int w = W > 0 ? W : ell_w;
-    const int wp = (w + 1) / 2;
-    const long long sb = blocks ? (long long)blocks[s] : s;                 // slice dictionary (sell8.hip)
-    const unsigned *cw = reinterpret_cast<const unsigned *>(buf + sb * ((long long)wp * 2048)) + t;
-    const unsigned *vw = cw + wp * 256;
-
-    V sum[NR][2];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) { sum[k][0] = V(0); sum[k][1] = V(0); }
-
-    if constexpr (W > 0) {
-        constexpr int WP = (W + 1) / 2;
-        unsigned c[WP], vc[WP];
-#pragma unroll
-        for (int jp = 0; jp < WP; ++jp) {
-            if (blocks) { c[jp] = cw[jp * 256]; vc[jp] = vw[jp * 256]; }           // pooled blocks: cached loads
-            else { c[jp] = __builtin_nontemporal_load(cw + jp * 256); vc[jp] = __builtin_nontemporal_load(vw + jp * 256); }
-        }
-        int d[W]; V val[W][2];
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            d[j] = s_delta[c0 < PAD8 ? c0 : c1];
-            val[j][0] = s_value[c0 < PAD8 ? (vc[j >> 1] >> (16 * (j & 1))) & 255u : 255u];          // entry 255 is 0.0
-            val[j][1] = s_value[c1 < PAD8 ? (vc[j >> 1] >> (16 * (j & 1) + 8)) & 255u : 255u];
-        }
-#pragma unroll
-        for (int k = 0; k < NR; ++k) {
-            V xv[W][2];
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-                gather_pair<V>(io.x[k], i, c0, c1, d[j], s_delta, deltas, xv[j][0], xv[j][1]);
-            }
-#pragma unroll
-            for (int j = 0; j < W; ++j)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) sum[k][q] += val[j][q] * xv[j][q];
-        }
-    } else {
-        for (int j = 0; j < w; ++j) {
-            const unsigned cword = cw[(j >> 1) * 256], vword = vw[(j >> 1) * 256];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int sh = 8 * ((j & 1) * 2 + q);
-                const unsigned code = (cword >> sh) & 255u;
-                if (code < PAD8) {
-                    const long long cidx = i + q + s_delta[code];
-                    const V v = s_value[(vword >> sh) & 255u];
+                    V v;
+                    if constexpr (VCODED) v = s_value[code_of(vword, j, q)];
+                    else v = vv[q];
 #pragma unroll
                     for (int k = 0; k < NR; ++k) sum[k][q] += v * io.x[k][cidx];
                 }
@@ -243,11 +150,11 @@ void spmm_sell_kernel(long long n, long long nslices, V alpha, int append, int e
     const long long s = traversal_block(trav, nslices);
     if (s < 0) return;
     const int r = 2 * threadIdx.x;
-    const long long i = s * ROWS + r;
+    const long long i = s * SLICE_ROWS + r;
     const int w = W > 0 ? W : ell_w;
-    const char *slice = sell + s * ((long long)w * ROWS * (4 + (long long)sizeof(V)));
+    const char *slice = sell + s * ((long long)w * SLICE_ROWS * (4 + (long long)sizeof(V)));
     const int *cp = reinterpret_cast<const int *>(slice) + r;
-    const V *vp = reinterpret_cast<const V *>(slice + (long long)w * ROWS * 4) + r;
+    const V *vp = reinterpret_cast<const V *>(slice + (long long)w * SLICE_ROWS * 4) + r;
     typedef typename vec2<V>::type V2;
 
     V sum[NR][2];
@@ -258,8 +165,8 @@ void spmm_sell_kernel(long long n, long long nslices, V alpha, int append, int e
         int2v c[W]; V2 v[W];
 #pragma unroll
         for (int j = 0; j < W; ++j) {
-            c[j] = __builtin_nontemporal_load(reinterpret_cast<const int2v *>(cp + j * ROWS));
-            v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * ROWS));
+            c[j] = __builtin_nontemporal_load(reinterpret_cast<const int2v *>(cp + j * SLICE_ROWS));
+            v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
         }
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
@@ -275,8 +182,8 @@ void spmm_sell_kernel(long long n, long long nslices, V alpha, int append, int e
         }
     } else {
         for (int j = 0; j < w; ++j) {
-            const int2v c = *reinterpret_cast<const int2v *>(cp + (long long)j * ROWS);
-            const V2 v = *reinterpret_cast<const V2 *>(vp + (long long)j * ROWS);
+            const int2v c = *reinterpret_cast<const int2v *>(cp + (long long)j * SLICE_ROWS);
+            const V2 v = *reinterpret_cast<const V2 *>(vp + (long long)j * SLICE_ROWS);
 #pragma unroll
             for (int q = 0; q < 2; ++q)
                 if (c[q] >= 0) {
@@ -295,8 +202,7 @@ void launch(hipStream_t s, long long grid, long long n, long long ns, V alpha, i
         const char *pool, const int *blocks)
 {
     with_width_of<3, 5, 7, 9>(w, [&](auto W) {    // unrolled for the usual stencil widths (1-D, 2-D 5/9-point, 3-D 7-point); any other width loops
-        if constexpr (CODES == 2) spmm_sell8v_kernel<V, W(), NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, values, cp, cc, cv, io, t, blocks);
-        else if constexpr (CODES == 1) spmm_sell8_kernel<V, W(), NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, cp, cc, cv, io, t, pool, blocks);
+        if constexpr (CODES > 0) spmm_coded_kernel<V, W(), NR, CODES == 2><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, deltas, values, cp, cc, cv, io, t, pool, blocks);
         else spmm_sell_kernel<V, W(), NR><<<(unsigned)grid, 256, 0, s>>>(n, ns, alpha, append, w, buf, cp, cc, cv, io, t);
     });
 }
@@ -315,7 +221,7 @@ int spmm(int dev, void *stream, int64_t n, int nrhs, V alpha, int append, int64_
     for (int k = 0; k < nrhs; ++k) VEXHIP_REQUIRE(x[k] && y[k], "NULL right-hand side or result");
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    const long long ns = (n + ROWS - 1) / ROWS;
+    const long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
     long long grid = 0;
     const trav_dev t = make_traversal(tr, ns, &grid);
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
@@ -324,12 +230,10 @@ int spmm(int dev, void *stream, int64_t n, int nrhs, V alpha, int append, int64_
         const int nr = nrhs - k0 < MAX_NR ? nrhs - k0 : MAX_NR;
         rhs_set<V> io;
         for (int k = 0; k < MAX_NR; ++k) { io.x[k] = x[k0 + (k < nr ? k : 0)]; io.y[k] = y[k0 + (k < nr ? k : 0)]; }
-        switch (nr) {
-            case 1: launch<V, CODES, 1>(s, grid, n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, io, t, pool, blocks); break;
-            case 2: launch<V, CODES, 2>(s, grid, n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, io, t, pool, blocks); break;
-            case 3: launch<V, CODES, 3>(s, grid, n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, io, t, pool, blocks); break;
-            default: launch<V, CODES, 4>(s, grid, n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, io, t, pool, blocks);
-        }
+        with_width<MAX_NR>(nr, [&](auto NR) {
+            if constexpr (NR() > 0)             // nr is 1..MAX_NR
+                launch<V, CODES, NR()>(s, grid, n, ns, alpha, append, (int)w, b, deltas, values, cp, cc, cv, io, t, pool, blocks);
+        });
         VEXHIP_LAUNCH_CHECK();
     }
     return 0;

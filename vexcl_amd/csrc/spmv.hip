@@ -17,6 +17,7 @@
 #include "pairing.hpp"
 #include "storage.hpp"
 #include "dispatch.hpp"
+#include "slices.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -29,8 +30,6 @@ namespace {
 typedef int    int2v  __attribute__((ext_vector_type(2)));
 typedef int    int4v  __attribute__((ext_vector_type(4)));
 typedef long long long2v __attribute__((ext_vector_type(2)));
-typedef double double2v __attribute__((ext_vector_type(2)));
-typedef float  float2v  __attribute__((ext_vector_type(2)));
 typedef float  float4v  __attribute__((ext_vector_type(4)));
 
 template <bool NT, typename T>
@@ -50,6 +49,7 @@ template <bool NT> __device__ __forceinline__ void load4(const long long *p, lon
     o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
 }
 template <bool NT> __device__ __forceinline__ void load4(const double *p, double (&o)[4]) {
+    typedef vec2<double>::type double2v;
     double2v a = ld<NT>(reinterpret_cast<const double2v *>(p));
     double2v b = ld<NT>(reinterpret_cast<const double2v *>(p) + 1);
     o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
@@ -314,13 +314,8 @@ __device__ __forceinline__ void ell_load(const int *cp, const V *vp, int (&c)[RP
     } else if constexpr (RPT == 2) {
         int2v cc = ld<NT>(reinterpret_cast<const int2v *>(cp));
         c[0] = cc.x; c[1] = cc.y;
-        if constexpr (sizeof(V) == 8) {
-            double2v vv = ld<NT>(reinterpret_cast<const double2v *>(vp));
-            v[0] = vv.x; v[1] = vv.y;
-        } else {
-            float2v vv = ld<NT>(reinterpret_cast<const float2v *>(vp));
-            v[0] = vv.x; v[1] = vv.y;
-        }
+        typename vec2<V>::type vv = ld<NT>(reinterpret_cast<const typename vec2<V>::type *>(vp));
+        v[0] = vv.x; v[1] = vv.y;
     } else {
         load4<NT>(cp, c);
         load4<NT>(vp, v);
@@ -396,8 +391,6 @@ void hell_kernel(long long n, long long nblocks, V alpha, int append,
 // entries per workgroup, and the column / value streams never collide on the same
 // memory channels.  Same arithmetic, same order.
 // ---------------------------------------------------------------------------
-constexpr int SELL_ROWS = 512;
-
 // XNT (A/B, round 6, VEXHIP_SELL_XLOAD=nt): the gathers of x as non-temporal loads -- does the memory system move less than a whole line
 // per 8-byte gather then?  (profiles/r06_unstructured_counters.log: it does not; TCC_EA0_RDREQ_32B stays 0)
 template <typename V, int W, bool NT, bool XNT = false>
@@ -410,18 +403,18 @@ void sell_kernel(long long n, long long nslices, V alpha, int append, int ell_w,
     const long long s = traversal_block(trav, nslices);
     if (s < 0) return;
     const int r = 2 * threadIdx.x;
-    const long long i = s * SELL_ROWS + r;
+    const long long i = s * SLICE_ROWS + r;
     const int w = W > 0 ? W : ell_w;
     // one contiguous region per slice: w*512 columns, then w*512 values
-    const char *slice = sell + s * ((long long)w * SELL_ROWS * (4 + (long long)sizeof(V)));
+    const char *slice = sell + s * ((long long)w * SLICE_ROWS * (4 + (long long)sizeof(V)));
     const int *cp = reinterpret_cast<const int *>(slice) + r;
-    const V *vp = reinterpret_cast<const V *>(slice + (long long)w * SELL_ROWS * 4) + r;
+    const V *vp = reinterpret_cast<const V *>(slice + (long long)w * SLICE_ROWS * 4) + r;
 
     V sum[2] = {V(0), V(0)};
     if constexpr (W > 0) {
         int c[W][2]; V v[W][2];
 #pragma unroll
-        for (int j = 0; j < W; ++j) ell_load<V, 2, NT>(cp + j * SELL_ROWS, vp + j * SELL_ROWS, c[j], v[j]);
+        for (int j = 0; j < W; ++j) ell_load<V, 2, NT>(cp + j * SLICE_ROWS, vp + j * SLICE_ROWS, c[j], v[j]);
         V xv[W][2];
 #pragma unroll
         for (int j = 0; j < W; ++j)
@@ -434,17 +427,12 @@ void sell_kernel(long long n, long long nslices, V alpha, int append, int ell_w,
     } else {
         for (int j = 0; j < w; ++j) {
             int c[2]; V v[2];
-            ell_load<V, 2, NT>(cp + j * SELL_ROWS, vp + j * SELL_ROWS, c, v);
+            ell_load<V, 2, NT>(cp + j * SLICE_ROWS, vp + j * SLICE_ROWS, c, v);
 #pragma unroll
             for (int q = 0; q < 2; ++q) if (c[q] >= 0) sum[q] += v[q] * (XNT ? __builtin_nontemporal_load(x + c[q]) : x[c[q]]);
         }
     }
-    if (csr_ptr) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (i + q < n)
-                for (int j = csr_ptr[i + q], e = csr_ptr[i + q + 1]; j < e; ++j) sum[q] += csr_val[j] * x[csr_col[j]];
-    }
+    add_csr_tail<V>(n, i, csr_ptr, csr_col, csr_val, &x, &sum);
     store_pair<V>(n, i, alpha, append, sum, y, trav);
 }
 
@@ -461,17 +449,17 @@ void sell_pair_kernel(long long n, long long nslices, V alpha, int append,
         const int *__restrict__ csr_ptr, const int *__restrict__ csr_col, const V *__restrict__ csr_val,
         const V *__restrict__ x, V *__restrict__ y, trav_dev trav)
 {
-    constexpr long long SLICE = (long long)W * SELL_ROWS * (4 + (long long)sizeof(V));
-    typedef V V2 __attribute__((ext_vector_type(2)));
+    constexpr long long SLICE = (long long)W * SLICE_ROWS * (4 + (long long)sizeof(V));
+    typedef typename vec2<V>::type V2;
     const long long s = traversal_block(trav, nslices);
     if (s < 0) return;
     const int r = 2 * threadIdx.x;
-    const long long i = s * SELL_ROWS + r;
+    const long long i = s * SLICE_ROWS + r;
     const int *cp = reinterpret_cast<const int *>(sell + s * SLICE) + r;
-    const V *vp = reinterpret_cast<const V *>(sell + s * SLICE + (long long)W * SELL_ROWS * 4) + r;
+    const V *vp = reinterpret_cast<const V *>(sell + s * SLICE + (long long)W * SLICE_ROWS * 4) + r;
     int c[W][2]; V v[W][2];
 #pragma unroll
-    for (int j = 0; j < W; ++j) ell_load<V, 2, true>(cp + j * SELL_ROWS, vp + j * SELL_ROWS, c[j], v[j]);
+    for (int j = 0; j < W; ++j) ell_load<V, 2, true>(cp + j * SLICE_ROWS, vp + j * SLICE_ROWS, c[j], v[j]);
     V xv[W][2];
 #pragma unroll
     for (int j = 0; j < W; ++j) {
@@ -499,12 +487,7 @@ void sell_pair_kernel(long long n, long long nslices, V alpha, int append,
     for (int j = 0; j < W; ++j)
 #pragma unroll
         for (int q = 0; q < 2; ++q) sum[q] += v[j][q] * xv[j][q];
-    if (csr_ptr) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (i + q < n)
-                for (int j = csr_ptr[i + q], e = csr_ptr[i + q + 1]; j < e; ++j) sum[q] += csr_val[j] * x[csr_col[j]];
-    }
+    add_csr_tail<V>(n, i, csr_ptr, csr_col, csr_val, &x, &sum);
     store_pair<V>(n, i, alpha, append, sum, y, trav);
 }
 
@@ -517,14 +500,14 @@ void sell_fill_kernel(long long n, long long nslices, int w,
         const int *__restrict__ max_col_p, char *__restrict__ sell)
 {
     const int max_col = *max_col_p;
-    for (long long pr = (long long)blockIdx.x * blockDim.x + threadIdx.x; pr < nslices * (SELL_ROWS / 2);
+    for (long long pr = (long long)blockIdx.x * blockDim.x + threadIdx.x; pr < nslices * (SLICE_ROWS / 2);
          pr += (long long)gridDim.x * blockDim.x) {
         const long long i = 2 * pr;
         long long b[2] = {0, 0}, e[2] = {0, 0};
         for (int q = 0; q < 2; ++q) if (i + q < n) { b[q] = ptr[i + q]; e[q] = ptr[i + q + 1]; }
-        char *slice = sell + (i / SELL_ROWS) * ((long long)w * SELL_ROWS * (4 + (long long)sizeof(V)));
-        int *sc = reinterpret_cast<int *>(slice) + (i % SELL_ROWS);
-        V *sv = reinterpret_cast<V *>(slice + (long long)w * SELL_ROWS * 4) + (i % SELL_ROWS);
+        char *slice = sell + (i / SLICE_ROWS) * ((long long)w * SLICE_ROWS * (4 + (long long)sizeof(V)));
+        int *sc = reinterpret_cast<int *>(slice) + (i % SLICE_ROWS);
+        V *sv = reinterpret_cast<V *>(slice + (long long)w * SLICE_ROWS * 4) + (i % SLICE_ROWS);
         pair_walk pw;
         pw.init(col, i, b[0], (int)min(e[0] - b[0], (long long)w), b[1], (int)min(e[1] - b[1], (long long)w), w);
         for (int j = 0; j < w; ++j) {
@@ -538,8 +521,8 @@ void sell_fill_kernel(long long n, long long nslices, int w,
                     const long long first = (long long)col[en[1 - q]] - (1 - q);     // where the partner's 16-byte load starts
                     c = (first >= 0 && first + 1 <= max_col) ? -1 : -2;
                 }
-                sc[j * SELL_ROWS + q] = c;
-                sv[j * SELL_ROWS + q] = v;
+                sc[j * SLICE_ROWS + q] = c;
+                sv[j * SLICE_ROWS + q] = v;
             }
         }
     }
@@ -653,7 +636,7 @@ void ell_offset_agree_kernel(long long n, int w, long long pitch, const int *__r
              i += (long long)gridDim.x * blockDim.x) {
             // pitch < 0: SELL-512 storage with (-pitch)-byte values; index in ints from the buffer start
             long long e = pitch > 0 ? i + j * pitch
-                                    : (i / SELL_ROWS) * ((long long)w * SELL_ROWS * (4 - pitch) / 4) + (long long)j * SELL_ROWS + i % SELL_ROWS;
+                                    : (i / SLICE_ROWS) * ((long long)w * SLICE_ROWS * (4 - pitch) / 4) + (long long)j * SLICE_ROWS + i % SLICE_ROWS;
             int c = ell_col[e];
             local += (c >= 0 && (long long)c - i == off) ? 1ull : 0ull;
         }
@@ -676,7 +659,7 @@ int spmv_sell(int dev, void *stream, int64_t n, V alpha, int append, int64_t w,
     const char *sc = static_cast<const char *>(sell);
     VEXHIP_SET_DEVICE(dev);
     hipStream_t s = as_stream(stream);
-    long long ns = (n + SELL_ROWS - 1) / SELL_ROWS;
+    long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
     long long grid = 0;
     const trav_dev order = attach(make_traversal(tr, ns, &grid), add);   // y = alpha A x + beta z (vexhip_spmat_apply_axpby_*): the kernels' store_pair adds it
     VEXHIP_REQUIRE(grid < (1ll << 31), "matrix too large for one launch");
@@ -698,8 +681,8 @@ int sell_fill(int dev, void *stream, int64_t n, const P *ptr, const int *col, co
     VEXHIP_REQUIRE(n >= 0 && w >= 1, "bad SELL geometry");
     if (n == 0) return 0;
     VEXHIP_SET_DEVICE(dev);
-    long long ns = (n + SELL_ROWS - 1) / SELL_ROWS;
-    int grid = (int)std::min<int64_t>((ns * (SELL_ROWS / 2) + 255) / 256, (int64_t)info(dev).cus * 16);
+    long long ns = (n + SLICE_ROWS - 1) / SLICE_ROWS;
+    int grid = (int)std::min<int64_t>((ns * (SLICE_ROWS / 2) + 255) / 256, (int64_t)info(dev).cus * 16);
     dev_buf<int> max_col;                                     // largest column of the ELL part (bounds the 16-byte gathers)
     VEXHIP_TRY(max_col.alloc(1));
     VEXHIP_TRY(hipMemsetAsync(max_col.p, 0xff, sizeof(int), as_stream(stream)));
@@ -820,7 +803,7 @@ static int build_order(int dev, void *stream, int64_t n, int64_t w, int64_t pitc
             for (int j = 0; j < w; ++j)
                 VEXHIP_TRY(hipMemcpyAsync(&sample[(size_t)k * w + j],
                             ell_col + (pitch > 0 ? rows[k] + j * pitch
-                                             : (rows[k] / SELL_ROWS) * (w * SELL_ROWS * (4 - pitch) / 4) + (int64_t)j * SELL_ROWS + rows[k] % SELL_ROWS),
+                                             : (rows[k] / SLICE_ROWS) * (w * SLICE_ROWS * (4 - pitch) / 4) + (int64_t)j * SLICE_ROWS + rows[k] % SLICE_ROWS),
                             sizeof(int), hipMemcpyDeviceToHost, s));
         }
         VEXHIP_TRY(hipStreamSynchronize(s));
@@ -952,7 +935,7 @@ int vexhip_spmv_hell_ordered_f32_i32(int dev, void *stream, int64_t n, float alp
         const vexhip_traversal *traversal)
 { return spmv_hell<float>(dev, stream, n, alpha, append, w, pitch, ec, ev, cp, cc, cv, x, y, traversal); }
 
-int64_t vexhip_sell_bytes(int64_t n, int64_t w, int value_bytes) { return (n + SELL_ROWS - 1) / SELL_ROWS * SELL_ROWS * w * (4 + value_bytes); }
+int64_t vexhip_sell_bytes(int64_t n, int64_t w, int value_bytes) { return (n + SLICE_ROWS - 1) / SLICE_ROWS * SLICE_ROWS * w * (4 + value_bytes); }
 
 int vexhip_sell_fill_f64_i32(int dev, void *stream, int64_t n, const int32_t *ptr, const int32_t *col, const double *val,
         int64_t w, void *sell)
