@@ -53,8 +53,9 @@ Launch geometry
   of sell8.hip `march_run`) -- visits every slice exactly once and that every other place is a hole.
 
 Left out
-  `sell8_pair_halo_kernel` (tests/test_gpu_distributed.py), `sell8v_runs_*` (reachable through vexhip_spmat only), the plane and grid
-  products, spmm.hip.  The `_dict` products with explicit maps, and `sell8_pair_kernel<W, *, true>` at the widths not named above.
+  `sell8_pair_halo_kernel` (tests/test_gpu_distributed.py), `sell8v_runs_*` (reachable through vexhip_spmat only), spmm.hip; the plane
+  and grid products and their plans have a file of their own, tests/test_gpu_plane_grid_kernels.py.  The `_dict` products with
+  explicit maps, and `sell8_pair_kernel<W, *, true>` at the widths not named above.
   The march plan looks at diagonals and slice numbers only: that a SELL8 matrix (stored values) is not given to
   the march product is the caller's business (vexhip_spmat asks for a plan for value-coded storage only) and is not tested here.
   The plan orders diagonals of equal magnitude as std::sort leaves them; the test matrices have no diagonal set for which that order
