@@ -1,5 +1,5 @@
-"""Direct parity tests of the plane and grid products -- vexcl_amd/csrc/plane.hip, plane32.hip, grid.hip, grid32.hip -- and of their plans,
-through the C ABI (`vexcl_amd.lib()`, `vexcl_amd._capi`) with torch tensors as device buffers.
+"""Direct parity tests of the plane and grid products -- vexcl_amd/csrc/plane.hip (`plane_walk`), plane32.hip (`plane32_walk`), grid.hip and
+grid32.hip (both `grid_walk<V, ...>` of grid_walk.hpp), all four over the shared pieces of walk.hpp -- and of their plans, through the C ABI (`vexcl_amd.lib()`, `vexcl_amd._capi`) with torch tensors as device buffers.
 
 What runs where
   * test_grid_products_on_hand_built_plans: `vexhip_spmv_sell8v_grid_f64` / `_f32` on plans filled by hand -- the geometry of

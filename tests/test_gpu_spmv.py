@@ -425,7 +425,7 @@ def _grid7_natural(nx, ny, nz, zero_face=False):
 
 
 def test_grid_product_is_bit_identical(T, oracle, built_lib):
-    """The grid product (round 4, grid.hip: the plane walk for grid lines of ANY length -- the matrix re-expressed by grid line,
+    """The grid product (round 4, grid.hip; the walk is grid_walk<double> of grid_walk.hpp: the plane walk for grid lines of ANY length -- the matrix re-expressed by grid line,
     a class per line) against the pair / streamed products AND the CSR restatement, bit for bit: the benchmark's operator on
     96^3 and 125^3 (odd line length: 16-byte requests at 8-byte addresses; odd lines per plane: the last tile stores one line),
     lines longer than 512 (one segment up to 1024 points, two beyond), 384- and 500-point lines, natural boundaries (nine line classes, explicit zeros),
@@ -939,7 +939,7 @@ def test_vector_added_float_store_pair_storages(T, oracle, built_lib, fmt, kw):
 
 
 def test_grid_product_fp32_is_bit_identical(T, oracle, built_lib):
-    """The fp32 grid product (round 5, grid32.hip: the walk of the fp64 grid product with FOUR rows per lane -- 16-byte requests at
+    """The fp32 grid product (round 5, grid32.hip: grid_walk<float> of grid_walk.hpp, the walk of the fp64 grid product with FOUR rows per lane -- 16-byte requests at
     4-byte addresses, the lane at the end of a line stores 1 .. 3 rows) against the pair product and the fp32 CSR restatement,
     bit for bit: the benchmark's operator on 96^3 and 125^3, line lengths that are no multiple of four (70, 125, 127, 250, 514,
     700, 1030 -- two segments), odd lines per plane, natural boundaries (nine classes, explicit zeros), full bands whose +-1
@@ -1166,7 +1166,7 @@ def test_two_dimensional_five_point_operators(T, oracle, built_lib):
 
 
 def test_plane_product_fp32_is_bit_identical(T, oracle, built_lib):
-    """The fp32 plane product (round 5, plane32.hip: the storage and the walk of the fp64 plane product with FOUR rows per lane, a
+    """The fp32 plane product (round 5, plane32.hip plane32_walk: the storage and the walk of the fp64 plane product -- the pieces of walk.hpp -- with FOUR rows per lane, a
     workgroup of two waves per pair of grid lines) against the pair product and the fp32 CSR restatement, bit for bit: small
     banded matrices through the forced plan (five dictionary blocks, lines that change their block from plane to plane, a
     ragged last plane, walks shorter than a group of four steps, several walk depths), '=' and '+= alpha'; the plan as the

@@ -26,9 +26,7 @@
 // The 512-point kernel stays the default where it applies (the headline): same walk, fewer scalar operands.
 // Compiled with -ffp-contract=off.
 #include "common.hpp"
-#include "halo.hpp"
-#include "lanes.hpp"
-#include "grid.hpp"
+#include "grid_walk.hpp"
 #include "storage.hpp"
 
 #include <algorithm>
@@ -533,292 +531,20 @@ void grid_probe_kernel(const P *__restrict__ ptr, const int *__restrict__ col, c
     }
 }
 
-// ---- the product ----
+// ---- the product: the walk of grid_walk.hpp on doubles ----
 // MAXT: 256 lanes (segments of <= 512 rows, four workgroups per CU) or 512 (segments of <= 1024 rows, two per CU: lines of 513 ..
 // 1024 points stay in one piece -- two 320-row segments of a 640-point line read x 1.87 times, profiles/r04_grid_pmc.json)
-// HALO (round 6; halo.hpp, the PULL form only): the launch is one device's whole product step.  x and y are addressed in the numbering of
-// the STORED grid, whose plane z0 - 1 / z1 (where the device has a neighbour) is a ghost plane: read from the neighbour's x in place
-// (H.lo / H.hi), behind its "x is final" flag where flags order the launches.  The walks are the plan's; the two that touch a ghost
-// plane are dispatched last and wait before they start.
-// ZM: the addend of the result (plane.hip): 0 none, 1 beta times the array zs ('+=': zs = y, beta = 1), 2 beta times x itself (from the registers)
-template <int ZM, int STORE_AUX, int MAXT, bool HALO>
-__device__ __forceinline__
-void grid_walk(const double *__restrict__ x, double *__restrict__ y, double alpha, const double *__restrict__ zs, double beta,
-        const int *__restrict__ line_class, const unsigned char *__restrict__ table, const double *__restrict__ values, const grid_dev &gd,
-        const halo_dev &H, [[maybe_unused]] const unsigned long long step)
-{
-    constexpr int TY = 2;
-    // LDS: the value table and the decoded values of the OTHER class, lane-private ([position * 2 + row][lane]: conflict-free)
-    __shared__ double s_value[256];
-    __shared__ double s_other[14][MAXT];
-
-    const int t = threadIdx.x;
-    const unsigned b = blockIdx.x, xcd = b & 7u, q = b >> 3;
-    int zc = (int)(q / (unsigned)gd.tpx);
-    int tile = (int)xcd * gd.tpx + (int)(q - (unsigned)zc * (unsigned)gd.tpx);
-    if (gd.cpx) { const int w = (int)(q / (unsigned)gd.tiles); tile = (int)(q - (unsigned)w * (unsigned)gd.tiles); zc = (int)xcd * gd.cpx + w; }      // (grid.hpp)
-    if (tile >= gd.tiles) return;                                   // the whole workgroup
-    const int ytile = tile / gd.segs, seg = tile - ytile * gd.segs;
-    const int y0 = TY * ytile;
-    const int nl = gd.ny - y0 < TY ? gd.ny - y0 : TY;               // lines of the tile inside a plane (odd ny: the last tile has one)
-    const int row0 = seg * gd.seg_len;
-    const int len = gd.nx - row0 < gd.seg_len ? gd.nx - row0 : gd.seg_len;
-    int z, zend_;
-    [[maybe_unused]] bool ghost_bad = false;
-    [[maybe_unused]] __shared__ int s_flag;
-    if constexpr (HALO) {
-        // the walks of the planes [z0, z1), the first and the last of them -- which touch a ghost plane -- dispatched behind the others
-        const int nch = (H.z1 - H.z0 + gd.depth - 1) / gd.depth;
-        const int c = nch > 1 ? (zc + 1) % nch : 0;
-        z = H.z0 + c * gd.depth; zend_ = z + gd.depth < H.z1 ? z + gd.depth : H.z1;
-        if (zc >= nch || z >= zend_) return;
-        ghost_bad = !halo_wait(H, step, H.lo && z == H.z0, H.hi && zend_ == H.z1, &s_flag);
-    } else {
-        z = zc * gd.depth;
-        zend_ = z + gd.depth < gd.nz ? z + gd.depth : gd.nz;
-        if (z >= zend_) return;
-    }
-    const int zend = zend_;
-    const int nx = gd.nx, ny = gd.ny;
-    // HALO: the elements of x and y that exist are those of the planes [z0, z1)
-    const long long own_lo = HALO ? (long long)H.z0 * ny * nx : 0;
-    const long long lines = HALO ? (long long)H.z1 * ny : gd.lines, x_last = HALO ? (long long)H.z1 * ny * nx - 1 : gd.x_last, n = HALO ? (long long)H.z1 * ny * nx : gd.n;
-    const unsigned lane_b = 16u * (unsigned)t;
-    const bool full = 2 * t + 1 < len, half = 2 * t + 1 == len;       // the lane stores a pair / its first row only / nothing
-    // the element beyond either end of the wave's 128 rows of a segment: lane 63 reads the one behind them, every other lane the
-    // one in front (lane 0 uses it; one cache line for the rest) -- byte offset from the start of the segment
-    const int edge_b = (t >> 6) * 1024 + ((t & 63) == 63 ? 1024 : -8);
-
-    for (int i = t; i < 256; i += (int)blockDim.x) s_value[i] = values[i];
-    __syncthreads();
-
-    // ---- a line class -> values (into s_other) and validity (returned) of this lane's rows at the seven positions ----
-    auto decode = [&](int cls) -> unsigned {
-        const unsigned char *tb = table + (long long)cls * 7 * gd.pitch + row0 + 2 * t;
-        unsigned bits = 0;
-#pragma unroll
-        for (int p = 0; p < 7; ++p) {
-            const unsigned c2 = *reinterpret_cast<const unsigned short *>(tb + (long long)p * gd.pitch);
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const unsigned code = (c2 >> (8 * r)) & 255u;
-                s_other[2 * p + r][t] = s_value[code];            // entry 255 of the value table is 0.0
-                bits |= (code != (unsigned)GR_ABSENT ? 1u : 0u) << (2 * p + r);
-            }
-        }
-        return bits;
-    };
-
-    const int hot = gd.hot;
-    double aH[7][2];                            // the hot class: values ...
-    unsigned long long mH[7][2];                // ... and the lanes with an entry, per position and row
-    {
-        const unsigned bitsH = decode(hot);
-#pragma unroll
-        for (int p = 0; p < 7; ++p) {
-            aH[p][0] = s_other[2 * p][t]; aH[p][1] = s_other[2 * p + 1][t];
-            mH[p][0] = __builtin_amdgcn_ballot_w64((bitsH >> (2 * p)) & 1u);
-            mH[p][1] = __builtin_amdgcn_ballot_w64((bitsH >> (2 * p + 1)) & 1u);
-        }
-    }
-    unsigned bitsO = 0;
-    int other = -1;                             // what s_other holds now is the hot class's: never asked for
-
-    // clamped requests (prologue, slow steps): line `l` of the tile's window (0 = the line above the tile, 1 .. TY = the tile,
-    // TY + 1 = the line below) in plane zz, element by element.  What lies outside x is never referenced by an entry; what is
-    // loaded in its place is multiplied by +0.0 behind a mask
-    auto elem = [&](long long i) -> double {
-        if constexpr (HALO) {
-            // an element of the plane below / above the device's planes: the neighbour's boundary plane of x, where it lies
-            const long long plane = (long long)ny * nx;
-            if (i < own_lo) { const long long j = i - (own_lo - plane); if (H.lo && j >= 0) return ghost_bad ? __builtin_nan("") : H.lo[j]; }
-            else if (i > x_last) { const long long j = i - (x_last + 1); if (H.hi && j < plane) return ghost_bad ? __builtin_nan("") : H.hi[j]; }
-            i = i < own_lo ? own_lo : i;
-        }
-        i = i < 0 ? 0 : i; i = i > x_last ? x_last : i; return x[i];
-    };
-    auto ld = [&](int zz, int l) -> d2 {
-        const long long i = ((long long)zz * ny + (y0 - 1 + l)) * nx + row0 + 2 * t;
-        d2 r; r.x = elem(i); r.y = elem(i + 1);
-        return r;
-    };
-    auto edge = [&](int zz, int l) -> double {
-        return elem(((long long)zz * ny + (y0 - 1 + l)) * nx + row0 + (edge_b >> 3));
-    };
-    auto yold = [&](int zz, int l) -> d2 {
-        long long i = ((long long)zz * ny + (y0 + l)) * nx + row0 + 2 * t, j = i + 1;
-        i = i < own_lo ? own_lo : i; i = i > n - 1 ? n - 1 : i; j = j < own_lo ? own_lo : j; j = j > n - 1 ? n - 1 : j;
-        d2 r; r.x = zs[i]; r.y = zs[j];
-        return r;
-    };
-
-    // ---- state at the top of the step for plane z: as in plane.hip ----
-    // Cs[0..3]: the tile's two centre lines in planes z-1, z, z+1, z+2;  Hs[0..1]: the halo lines (above, below) in planes z, z+1;
-    // Es[0..1]: per centre line the edge element of this lane in planes z, z+1.  The fast loop runs GROUPS of four steps with
-    // the names rotated; every request has two steps to arrive.
-    d2 Cs[4][TY], Hs[2][2], Yo[TY];
-    double Es[2][TY];
-    const unsigned line_b = (unsigned)nx * 8u;                        // bytes from a line to the next
-    const unsigned plane_b32 = (unsigned)ny * line_b;                 // ... to the same line of the next plane (the plan: (depth + 4) of them < 2^32)
-    const int z_first = z;
-    // buffer resources of the fast loop: x from the segment of the line above the tile in the workgroup's first plane, y from
-    // the tile's first line in that plane.  No range check (the scalar offset that moves with the planes takes no part in it):
-    // the fast loop only runs where every request of every lane lies inside the arrays (zh below)
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<double *>(x + (((long long)z_first * ny + (y0 - 1)) * nx + row0)), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + (((long long)z_first * ny + y0) * nx + row0), 0, -1, 0x00020000);
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(ZM == 1 ? zs : x) + (((long long)z_first * ny + y0) * nx + row0), 0, -1, 0x00020000);
-#pragma unroll
-    for (int l = 0; l < TY; ++l) { Cs[0][l] = ld(z - 1, l + 1); Cs[1][l] = ld(z, l + 1); Cs[2][l] = ld(z + 1, l + 1); Cs[3][l] = ld(z + 2, l + 1); }
-    // gd.flat (round 6): no entry at +-nx anywhere -- a 5-point operator on a 2-D grid, its rows cut into virtual lines: the lines above
-    // and below the tile are never requested (two of the six 16-byte requests of a step)
-    const bool flat = gd.flat != 0;                                   // uniform
-    const d2 dzero = {0.0, 0.0};
-    Hs[0][0] = Hs[0][1] = Hs[1][0] = Hs[1][1] = dzero;
-    if (!flat) { Hs[0][0] = ld(z, 0); Hs[0][1] = ld(z, TY + 1); Hs[1][0] = ld(z + 1, 0); Hs[1][1] = ld(z + 1, TY + 1); }
-#pragma unroll
-    for (int l = 0; l < TY; ++l) {
-        Es[0][l] = edge(z, l + 1); Es[1][l] = edge(z + 1, l + 1);
-        if (ZM == 1) Yo[l] = yold(z, l);
-    }
-
-    // the lane's sums for tile line l: x at the seven positions from the registers named above
-#define GRID_XS(P, C, N, H, E, l)                                                                                                    \
-        const d2 c = C[l], up = (l) == 0 ? H[0] : C[(l) > 0 ? (l) - 1 : 0], dn = (l) == TY - 1 ? H[1] : C[(l) < TY - 1 ? (l) + 1 : 0];                                                  \
-        const double xs0[7] = {P[l].x, up.x, shift_from_lower_lane(c.y, E[l]), c.x, c.y, dn.x, N[l].x};                                \
-        const double xs1[7] = {P[l].y, up.y, c.x, c.y, shift_from_upper_lane(c.x, E[l]), dn.y, N[l].y};
-#define GRID_HOT_SUMS(s0, s1)                                                                                                        \
-        _Pragma("unroll") for (int p = 0; p < 7; ++p) { s0 += aH[p][0] * keep_lanes(xs0[p], mH[p][0]); s1 += aH[p][1] * keep_lanes(xs1[p], mH[p][1]); }
-#define GRID_OTHER_SUMS(s0, s1)                                                                                                      \
-        _Pragma("unroll") for (int p = 0; p < 7; ++p) {                                                                               \
-            s0 += s_other[2 * p][t] * keep_bit(xs0[p], bitsO, 2 * p); s1 += s_other[2 * p + 1][t] * keep_bit(xs1[p], bitsO, 2 * p + 1); }
-
-    // fast steps: every request lies inside the arrays.  A lane may sit beyond the end of its line (it stores nothing, but it
-    // requests): `over` = the furthest element, from the start of a line, that a lane of this workgroup asks for
-    int zh = zend;
-    {
-        const long long over = row0 + 2 * (long long)blockDim.x + 1;
-        const long long xl_in = x_last - over >= 0 ? (x_last - over) / nx : -1;       // largest line all of whose requests are inside x
-        const long long yl_in = n - 1 - over >= 0 ? (n - 1 - over) / nx : -1;         // ... inside y ('+=' reads the old y one plane ahead)
-        // largest z with (z + ahead) * ny + y0 + line <= limit, + 1
-        auto end_for = [&](long long limit, int ahead, int line) -> long long { const long long v = limit - y0 - line; return v < 0 ? 0 : v / ny - ahead + 1; };
-        long long e = end_for(xl_in, 3, TY);                                           // x: planes up to z + 3, lines up to the one below the tile
-        e = std::min(e, end_for(lines - 1, 0, TY - 1));                               // y: both lines exist
-        if (ZM == 1) e = std::min(e, end_for(yl_in, 1, TY - 1));
-        zh = zh < e ? zh : (int)(e < 0 ? 0 : e);
-    }
-
-    while (z < zend) {
-        // ---- how many of the next planes (<= 64) can take fast steps: both lines use the hot class or the other class ----
-        unsigned long long use_hot[TY];          // bit k: line l of plane z + k uses the hot class (else: the other class)
-        int run;
-        {
-            const int k = t & 63, zz = z + k;
-            const bool in = zz < zh;
-            bool ok = in;
-#pragma unroll
-            for (int l = 0; l < TY; ++l) {
-                const int bk = (in && l < nl) ? line_class[(long long)zz * ny + (y0 + l)] : hot;
-                ok = ok && (bk == hot || bk == other);
-                use_hot[l] = __builtin_amdgcn_ballot_w64(bk == hot);
-            }
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-            run = ~m ? __builtin_ctzll(~m) : 64;
-        }
-        if (run >= 4) {
-            // xo: plane z + 2, the line above the tile; yo: plane z, the tile's first line; both relative to the workgroup's first plane
-            unsigned xo = (unsigned)((z + 2 - z_first) * plane_b32), yo = (unsigned)((z - z_first) * plane_b32);
-            auto fast_step = [&](d2 (&P)[TY], d2 (&C)[TY], d2 (&N)[TY], d2 (&H)[2], double (&E)[TY]) {
-                d2 o[TY];
-#pragma unroll
-                for (int l = 0; l < TY; ++l) {
-                    GRID_XS(P, C, N, H, E, l)
-                    double s0 = 0.0, s1 = 0.0;
-                    if (use_hot[l] & 1ull) { GRID_HOT_SUMS(s0, s1) } else { GRID_OTHER_SUMS(s0, s1) }      // uniform
-                    o[l].x = alpha * s0; o[l].y = alpha * s1;
-                    if (ZM == 1) { o[l].x = beta * Yo[l].x + o[l].x; o[l].y = beta * Yo[l].y + o[l].y; }
-                    if (ZM == 2) { o[l].x = beta * c.x + o[l].x; o[l].y = beta * c.y + o[l].y; }
-                }
-#pragma unroll
-                for (int l = 0; l < TY; ++l) use_hot[l] >>= 1;
-#pragma unroll
-                for (int l = 0; l < TY; ++l)
-                    if (l < nl) {                  // uniform; written once, not read again by this kernel
-                        if (full) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, o[l]), ry, (int)lane_b, (int)(yo + l * line_b), STORE_AUX);
-                        else if (half) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, o[l].x), ry, (int)lane_b, (int)(yo + l * line_b), STORE_AUX);
-                    }
-                if (ZM == 1) {
-#pragma unroll
-                    for (int l = 0; l < TY; ++l) Yo[l] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rz, (int)lane_b, (int)(yo + plane_b32 + l * line_b), 0));
-                }
-                if (!flat) {
-                    H[0] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)xo, 0));
-                    H[1] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)(xo + (TY + 1) * line_b), 0));
-                }
-#pragma unroll
-                for (int l = 0; l < TY; ++l) {
-                    P[l] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)(xo + plane_b32 + (l + 1) * line_b), 0));
-                    E[l] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rx, edge_b + 8, (int)(xo + (l + 1) * line_b - 8u), 0));
-                }
-                xo += plane_b32; yo += plane_b32; ++z;
-            };
-            for (int g = run >> 2; g > 0; --g) {
-                fast_step(Cs[0], Cs[1], Cs[2], Hs[0], Es[0]);
-                fast_step(Cs[1], Cs[2], Cs[3], Hs[1], Es[1]);
-                fast_step(Cs[2], Cs[3], Cs[0], Hs[0], Es[0]);
-                fast_step(Cs[3], Cs[0], Cs[1], Hs[1], Es[1]);
-            }
-            if (run == 64) continue;                                      // look again: the run may go on
-        }
-        if (z >= zend) break;
-        // ---- a slow step: a line needs another class decoded, the last planes (clamped requests), the ragged last plane, what
-        // a run leaves over after its groups of four; names rotated by copies ----
-#pragma unroll
-        for (int l = 0; l < TY; ++l) {
-            const long long li = (long long)z * ny + (y0 + l);
-            if (l < nl && li < lines) {                                   // uniform
-                GRID_XS(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l)
-                double s0 = 0.0, s1 = 0.0;
-                const int cls = __builtin_amdgcn_readfirstlane(line_class[li]);
-                if (cls == hot) { GRID_HOT_SUMS(s0, s1) }
-                else {
-                    if (cls != other) { bitsO = decode(cls); other = cls; }
-                    GRID_OTHER_SUMS(s0, s1)
-                }
-                d2 o; o.x = alpha * s0; o.y = alpha * s1;
-                if (ZM == 1) { o.x = beta * Yo[l].x + o.x; o.y = beta * Yo[l].y + o.y; }
-                if (ZM == 2) { o.x = beta * c.x + o.x; o.y = beta * c.y + o.y; }
-                double *yr = y + li * nx + row0 + 2 * t;
-                if (full || half) __builtin_nontemporal_store(o.x, yr);
-                if (full) __builtin_nontemporal_store(o.y, yr + 1);
-            }
-        }
-#pragma unroll
-        for (int l = 0; l < TY; ++l) {
-            Cs[0][l] = Cs[1][l]; Cs[1][l] = Cs[2][l]; Cs[2][l] = Cs[3][l]; Cs[3][l] = ld(z + 3, l + 1);
-            Es[0][l] = Es[1][l]; Es[1][l] = edge(z + 2, l + 1);
-            if (ZM == 1) Yo[l] = yold(z + 1, l);
-        }
-#pragma unroll
-        for (int l = 0; l < 2; ++l) { Hs[0][l] = Hs[1][l]; if (!flat) Hs[1][l] = ld(z + 2, (TY + 1) * l); }
-        ++z;
-    }
-#undef GRID_XS
-#undef GRID_HOT_SUMS
-#undef GRID_OTHER_SUMS
-}
-
 template <int ZM, int STORE_AUX, int MAXT, bool HALO = false>
 __global__ __launch_bounds__(MAXT, MAXT == 256 ? 4 : 2)
 void sell8_grid_kernel(const double *__restrict__ x, double *__restrict__ y, double alpha, const double *__restrict__ zs, double beta,
         const int *__restrict__ line_class, const unsigned char *__restrict__ table, const double *__restrict__ values, grid_dev gd, halo_dev H)
 {
     if constexpr (!HALO) {
-        grid_walk<ZM, STORE_AUX, MAXT, false>(x, y, alpha, zs, beta, line_class, table, values, gd, H, 0ull);
+        grid_walk<double, ZM, STORE_AUX, MAXT, false>(x, y, alpha, zs, beta, line_class, table, values, gd, H, 0ull);
     } else {
         const unsigned long long step = *H.step;
         halo_announce(H, step);
-        grid_walk<ZM, STORE_AUX, MAXT, true>(x, y, alpha, zs, beta, line_class, table, values, gd, H, step);
+        grid_walk<double, ZM, STORE_AUX, MAXT, true>(x, y, alpha, zs, beta, line_class, table, values, gd, H, step);
         halo_finish(H, step);
     }
 }

@@ -25,7 +25,7 @@
 // within a row (so that position order IS storage order) -- and declines otherwise; the march and pair products remain.
 // Compiled with -ffp-contract=off.
 #include "common.hpp"
-#include "lanes.hpp"
+#include "walk.hpp"
 #include "halo.hpp"
 #include "plane.hpp"
 #include "storage.hpp"
@@ -37,6 +37,43 @@
 
 namespace vexhip {
 namespace {
+
+constexpr int PL_LINE_B = PL_ROWS * 8;             // bytes of a line
+
+// One workgroup's piece of a push: elements [j * per, (j + 1) * per) of the rank's first (down) or last boundary plane of x go into
+// the neighbour's window in 16-byte pieces; the workgroup is counted (if `counted`), and the one that brings the count to `target`
+// raises `arrive` at the neighbour.  s_flag: one LDS word of the caller.
+__device__ __forceinline__ void push_piece(const double *__restrict__ x, int far, const halo_dev &H, unsigned long long step, bool down, int j,
+        int per, unsigned target, bool counted, int *s_flag)
+{
+    const int t = threadIdx.x;
+    if (t == 0) *s_flag = spin_until(down ? H.sent_lo : H.sent_hi, step - 1ull, H.err, H.ticks, 0) ? 1 : 0;   // the neighbour has read the previous share
+    __syncthreads();
+    if (!*s_flag) return;                                                    // uniform; a neighbour that does not answer is not written to
+    const double *src = x + (down ? (long long)H.z0 * far : (long long)(H.z1 - 1) * far);
+    double *dst = down ? H.dst_lo : H.dst_hi;
+    const int i0 = j * per, i1 = i0 + per < H.halo ? i0 + per : H.halo;
+    for (int i = i0 + 2 * t; i < i1; i += 512)
+        *reinterpret_cast<d2 *>(dst + i) = *reinterpret_cast<const d2 *>(src + i);
+    // The window is UNCACHED memory (here and through the peer mapping): its stores go past every cache, and a wave's
+    // stores have been performed at the destination once its store counter is back at zero -- so the flag may follow
+    // behind `s_waitcnt vmcnt(0)` + a barrier + a relaxed count of the workgroups, with NO release fence.  A fence at
+    // agent or system scope writes back the XCD's L2, which at this moment is full of the product's freshly stored y:
+    // with ACQ_REL counts and a system fence in front of the flag the push of 4 MB took ~50 us of a 120 us step
+    // (tools/r05_dist_step.py, VEXHIP_HALO_NO_PUSH against the default; profiles/r05_dist_step_*.json).
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0 && counted) {
+        unsigned *cnt = H.done + (down ? 1 : 2);
+        const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old + 1u == target) {
+            __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (H.release) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");       // a window in cached memory (diagnostic): the model-correct hand-off
+            __hip_atomic_store(down ? H.peer_arrive_lo : H.peer_arrive_hi, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
 
 // HALO (round 5, halo.hpp): the launch is one rank's whole product step.  x and y are addressed in the numbering of the STORED
 // grid, whose plane z0 - 1 / z1 (if the rank has a neighbour there) is a ghost plane: its lines are read from the rank's window
@@ -74,37 +111,11 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         halo_announce(H, step);
         const unsigned npush = H.pull ? 0u : (H.dst_lo ? (unsigned)H.push_blocks : 0u) + (H.dst_hi ? (unsigned)H.push_blocks : 0u);
         if (b < npush) {
-            // ---- copy one of the rank's boundary planes into the neighbour's window (16-byte pieces), raise `arrive` there ----
+            // ---- a dedicated push workgroup: every one of the push_blocks per side is counted, whether a piece is left for it or not ----
             const bool down = H.dst_lo && b < (unsigned)H.push_blocks;           // the FIRST plane goes to the lower neighbour
             const unsigned j = down ? b : b - (H.dst_lo ? (unsigned)H.push_blocks : 0u);
-            if (t == 0) s_flag[0] = spin_until(down ? H.sent_lo : H.sent_hi, step - 1ull, H.err, H.ticks, 0) ? 1 : 0;   // the neighbour has read the previous share
-            __syncthreads();
-            if (s_flag[0]) {                                                     // uniform; a neighbour that does not answer is not written to
-                const double *src = x + (down ? (long long)H.z0 * pd.far : (long long)(H.z1 - 1) * pd.far);
-                double *dst = down ? H.dst_lo : H.dst_hi;
-                const int per = ((H.halo + H.push_blocks - 1) / H.push_blocks + 511) / 512 * 512;
-                const int i0 = (int)j * per, i1 = i0 + per < H.halo ? i0 + per : H.halo;
-                for (int i = i0 + 2 * t; i < i1; i += 512)
-                    *reinterpret_cast<d2 *>(dst + i) = *reinterpret_cast<const d2 *>(src + i);
-                // The window is UNCACHED memory (here and through the peer mapping): its stores go past every cache, and a wave's
-                // stores have been performed at the destination once its store counter is back at zero -- so the flag may follow
-                // behind `s_waitcnt vmcnt(0)` + a barrier + a relaxed count of the workgroups, with NO release fence.  A fence at
-                // agent or system scope writes back the XCD's L2, which at this moment is full of the product's freshly stored y:
-                // with ACQ_REL counts and a system fence in front of the flag the push of 4 MB took ~50 us of a 120 us step
-                // (tools/r05_dist_step.py, VEXHIP_HALO_NO_PUSH against the default; profiles/r05_dist_step_*.json).
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (t == 0) {
-                    unsigned *cnt = H.done + (down ? 1 : 2);
-                    const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (old + 1u == (unsigned)H.push_blocks) {
-                        __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (H.release) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");       // a window in cached memory (diagnostic): the model-correct hand-off
-                        __hip_atomic_store(down ? H.peer_arrive_lo : H.peer_arrive_hi, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                }
-            }
+            const int per = ((H.halo + H.push_blocks - 1) / H.push_blocks + 511) / 512 * 512;
+            push_piece(x, pd.far, H, step, down, (int)j, per, (unsigned)H.push_blocks, true, &s_flag[0]);
             if (H.debug && t == 0) { unsigned long long *d = H.debug + 6ull * blockIdx.x; d[0] = dbg_t0; d[1] = 0; d[2] = 0; d[3] = wall_clock64(); d[4] = ~0ull; d[5] = down ? 0ull : 1ull; }
             return;
         }
@@ -146,32 +157,9 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         if (!H.pull && H.push_blocks == 0 && b < 512u) {
             const bool down = b < 256u;
             double *dst = down ? H.dst_lo : H.dst_hi;
-            if (dst) {                                                           // uniform
-                if (t == 0) s_flag[0] = spin_until(down ? H.sent_lo : H.sent_hi, step - 1ull, H.err, H.ticks, 0) ? 1 : 0;
-                __syncthreads();
-                if (s_flag[0]) {
-                    const double *src = x + (down ? (long long)H.z0 * pd.far : (long long)(H.z1 - 1) * pd.far);
-                    const int per = ((H.halo + 255) / 256 + 511) / 512 * 512;
-                    const int i0 = (int)(b & 255u) * per, i1 = i0 + per < H.halo ? i0 + per : H.halo;
-                    for (int i = i0 + 2 * t; i < i1; i += 512)
-                        *reinterpret_cast<d2 *>(dst + i) = *reinterpret_cast<const d2 *>(src + i);
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __syncthreads();
-                    if (t == 0) {
-                        unsigned *cnt = H.done + (down ? 1 : 2);
-                        const unsigned npieces = (unsigned)((H.halo + per - 1) / per);
-                        const bool mine = i0 < H.halo;
-                        if (mine) {
-                            const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if (old + 1u == npieces) {
-                                __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                if (H.release) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                                __hip_atomic_store(down ? H.peer_arrive_lo : H.peer_arrive_hi, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                            }
-                        }
-                    }
-                }
+            if (dst) {                                                           // uniform; only the workgroups that have a piece are counted
+                const int per = ((H.halo + 255) / 256 + 511) / 512 * 512, j = (int)(b & 255u);
+                push_piece(x, pd.far, H, step, down, j, per, (unsigned)((H.halo + per - 1) / per), j * per < H.halo, &s_flag[0]);
                 __syncthreads();                                                 // s_flag is used again by the ghost waits
             }
         }
@@ -190,21 +178,8 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
     // ---- a dictionary block -> values (into s_other) and validity (returned) of this lane's rows at the seven positions ----
     const int wp = (pd.w + 1) >> 1;
     auto decode = [&](int blk) -> unsigned {
-        if (pd.pitch > 0) {                      // the matrix stored by grid line (grid.hip): a value code per position and row, 255 = no entry
-            const char *tb = pool + (long long)blk * 7 * pd.pitch + 2 * t;
-            unsigned bits = 0;
-#pragma unroll
-            for (int p = 0; p < 7; ++p) {
-                const unsigned c2 = *reinterpret_cast<const unsigned short *>(tb + (long long)p * pd.pitch);
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const unsigned code = (c2 >> (8 * r)) & 255u;
-                    s_other[2 * p + r][t] = s_value[code];            // entry 255 of the value table is 0.0
-                    bits |= (code != 255u ? 1u : 0u) << (2 * p + r);
-                }
-            }
-            return bits;
-        }
+        // the matrix stored by grid line (grid.hip): a value code per position and row, 255 = no entry
+        if (pd.pitch > 0) return decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 2 * t, pd.pitch, s_value, s_other, t);
         const unsigned *cw = reinterpret_cast<const unsigned *>(pool + (long long)blk * ((long long)wp * 2048)) + t;
         unsigned dcw[4], vcw[4];                // diagonal codes, value codes: one word per pair of ELL columns
 #pragma unroll
@@ -230,15 +205,7 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
     const int hot = pd.hot;
     double aH[7][2];                            // the hot block: values ...
     unsigned long long mH[7][2];                // ... and the lanes with an entry, per position and row
-    {
-        const unsigned bitsH = decode(hot);
-#pragma unroll
-        for (int p = 0; p < 7; ++p) {
-            aH[p][0] = s_other[2 * p][t]; aH[p][1] = s_other[2 * p + 1][t];
-            mH[p][0] = __builtin_amdgcn_ballot_w64((bitsH >> (2 * p)) & 1u);
-            mH[p][1] = __builtin_amdgcn_ballot_w64((bitsH >> (2 * p + 1)) & 1u);
-        }
-    }
+    take_hot(decode(hot), s_other, t, aH, mH);
     unsigned bitsO = 0;
     int other = -1;                             // what s_other holds now is the hot block's: never asked for
 
@@ -308,21 +275,14 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(zs + (long long)li * PL_ROWS) + lane_b);
     };
 
-    // ---- state at the top of the step for plane z (canonical naming) ----
-    // Cs[0..3]: the tile's two centre lines in planes z-1, z, z+1, z+2;  Hs[0..1]: the halo lines (above, below) in planes z, z+1;
-    // Es[0..1]: per centre line the edge element of this lane (lane 0: the one in front of the wave's rows, lane 63: the one behind)
-    // in planes z, z+1.  A step consumes plane z-1's centres and plane z's halos and edges and requests into the SAME registers
-    // what plays that role three (centres) or two planes later: every request has two steps to arrive.  The fast loop runs
-    // GROUPS of four steps with the names rotated: after four steps every name is back in place and no register is copied (a
-    // copy behind a request makes the step wait for it: the one-step form of this loop ran 8 % slower).  It contains no memory
-    // instruction other than these requests and the stores, so that the waits of a step count what the step before requested;
-    // which block a line uses is known for up to 64 planes ahead (one look at blocks[] per entry).
+    // ---- the registers of the walk (walk.hpp), filled for plane z; which block a line uses is known for up to 64 planes ahead
+    // (fast_run: one look at blocks[] per entry) ----
     constexpr int NPASS = HALO ? 2 : 1;
     for (int pass = 0; pass < NPASS; ++pass) {
     if constexpr (HALO) if (pass == 1) { if (!second) break; z = z2; zend = zend2; }
     d2 Cs[4][TY], Hs[2][2], Yo[TY];
     double Es[2][TY];
-    const unsigned plane_b32 = (unsigned)ny * (PL_ROWS * 8u);          // bytes from a line to the same line of the next plane (the plan: (depth + 4) of them < 2^32)
+    const unsigned plane_b32 = (unsigned)ny * (unsigned)PL_LINE_B;     // bytes from a line to the same line of the next plane (the plan: (depth + 4) of them < 2^32)
     const int z_first = z;
     // buffer resources of the fast loop: x from the line above the tile in the workgroup's first plane, y from the tile's first
     // line in that plane (no range check: the fast loop only runs where every request lies inside the arrays)
@@ -330,26 +290,7 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         const_cast<double *>(x + ((long long)z_first * ny + (y0 - 1)) * PL_ROWS), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(ZM == 1 ? zs : x) + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
-#pragma unroll
-    for (int l = 0; l < TY; ++l) { Cs[0][l] = ld(z - 1, l + 1); Cs[1][l] = ld(z, l + 1); Cs[2][l] = ld(z + 1, l + 1); Cs[3][l] = ld(z + 2, l + 1); }
-    if constexpr (FLAT) { const d2 dzero = {0.0, 0.0}; Hs[0][0] = Hs[0][1] = Hs[1][0] = Hs[1][1] = dzero; }
-    else { Hs[0][0] = ld(z, 0); Hs[0][1] = ld(z, TY + 1); Hs[1][0] = ld(z + 1, 0); Hs[1][1] = ld(z + 1, TY + 1); }
-#pragma unroll
-    for (int l = 0; l < TY; ++l) {
-        Es[0][l] = edge(z, l + 1); Es[1][l] = edge(z + 1, l + 1);
-        if (ZM == 1) Yo[l] = yold(z, l);
-    }
-
-    // the lane's sums for tile line l: x at the seven positions from the registers named above
-#define PLANE_XS(P, C, N, H, E, l)                                                                                                   \
-        const d2 c = C[l], up = (l) == 0 ? H[0] : C[(l) > 0 ? (l) - 1 : 0], dn = (l) == TY - 1 ? H[1] : C[(l) < TY - 1 ? (l) + 1 : 0];                                                  \
-        const double xs0[7] = {P[l].x, up.x, shift_from_lower_lane(c.y, E[l]), c.x, c.y, dn.x, N[l].x};                                \
-        const double xs1[7] = {P[l].y, up.y, c.x, c.y, shift_from_upper_lane(c.x, E[l]), dn.y, N[l].y};
-#define PLANE_HOT_SUMS(s0, s1)                                                                                                       \
-        _Pragma("unroll") for (int p = 0; p < 7; ++p) { s0 += aH[p][0] * keep_lanes(xs0[p], mH[p][0]); s1 += aH[p][1] * keep_lanes(xs1[p], mH[p][1]); }
-#define PLANE_OTHER_SUMS(s0, s1)                                                                                                     \
-        _Pragma("unroll") for (int p = 0; p < 7; ++p) {                                                                               \
-            s0 += s_other[2 * p][t] * keep_bit(xs0[p], bitsO, 2 * p); s1 += s_other[2 * p + 1][t] * keep_bit(xs1[p], bitsO, 2 * p + 1); }
+    fill_registers<ZM>(Cs, Hs, Es, Yo, z, !FLAT, ld, edge, yold);
 
     // fast steps need nothing clamped: planes up to z + 3 inside x, both lines inside y
     int zh = zend;
@@ -360,96 +301,65 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
     }
 
     while (z < zend) {
-        // ---- how many of the next planes (<= 64) can take fast steps: both lines use the hot block or the other block ----
-        unsigned long long use_hot[TY];          // bit k: line l of plane z + k uses the hot block (else: the other block)
-        int run;
-        {
-            const int k = t & 63, zz = z + k;
-            const bool in = zz < zh;
-            bool ok = in;
-#pragma unroll
-            for (int l = 0; l < TY; ++l) {
-                const int bk = in ? blocks[(long long)zz * ny + (y0 + l)] : hot;
-                ok = ok && (bk == hot || bk == other);
-                use_hot[l] = __builtin_amdgcn_ballot_w64(bk == hot);
-            }
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-            run = ~m ? __builtin_ctzll(~m) : 64;
-        }
+        unsigned long long use_hot[TY];
+        const int run = fast_run(blocks, ny, y0, TY, z, zh, hot, other, t, use_hot);
         if (run >= 4) {
             // Buffer addressing: a resource per array (scalar), the lane's byte offset (ONE vector register for the whole
             // kernel) and a scalar offset that moves with the planes -- no 64-bit vector address arithmetic, which cost a dozen
             // registers and, re-using the registers of requests still in flight, forced early waits.  xo: plane z + 2, the
             // line above the tile; yo: plane z, the tile's first line; both relative to the workgroup's first plane.
             unsigned xo = (unsigned)((z + 2 - z_first) * plane_b32), yo = (unsigned)((z - z_first) * plane_b32);
-            auto fast_step = [&](d2 (&P)[TY], d2 (&C)[TY], d2 (&N)[TY], d2 (&H)[2], double (&E)[TY]) {
+            auto fast_step = [&](d2 (&P)[TY], d2 (&C)[TY], d2 (&N)[TY], d2 (&Hl)[2], double (&E)[TY]) {
                 d2 o[TY];
 #pragma unroll
                 for (int l = 0; l < TY; ++l) {
-                    PLANE_XS(P, C, N, H, E, l)
-                    double s0 = 0.0, s1 = 0.0;
-                    if (use_hot[l] & 1ull) { PLANE_HOT_SUMS(s0, s1) } else { PLANE_OTHER_SUMS(s0, s1) }      // uniform
-                    o[l].x = alpha * s0; o[l].y = alpha * s1;
-                    if (ZM == 1) { o[l].x = beta * Yo[l].x + o[l].x; o[l].y = beta * Yo[l].y + o[l].y; }
-                    if (ZM == 2) { o[l].x = beta * c.x + o[l].x; o[l].y = beta * c.y + o[l].y; }
+                    double xs[2][7], s[2] = {};
+                    stencil_x(P, C, N, Hl, E, l, xs);
+                    if (use_hot[l] & 1ull) hot_sums(s, aH, mH, xs); else other_sums(s, s_other, t, bitsO, xs);      // uniform
+                    o[l] = add_addend<ZM>(alpha, s, beta, Yo[l], C[l]);
                 }
 #pragma unroll
                 for (int l = 0; l < TY; ++l) use_hot[l] >>= 1;
 #pragma unroll
-                for (int l = 0; l < TY; ++l)       // written once, not read again by this kernel
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, o[l]), ry, (int)lane_b, (int)(yo + l * 4096u), STORE_AUX);
+                for (int l = 0; l < TY; ++l) store16<STORE_AUX>(o[l], ry, (int)lane_b, yo + l * PL_LINE_B);       // written once, not read again by this kernel
                 if (ZM == 1) {
 #pragma unroll
-                    for (int l = 0; l < TY; ++l) Yo[l] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rz, (int)lane_b, (int)(yo + plane_b32 + l * 4096u), 0));
+                    for (int l = 0; l < TY; ++l) Yo[l] = load16<double>(rz, (int)lane_b, yo + plane_b32 + l * PL_LINE_B);
                 }
                 if constexpr (!FLAT) {
-                    H[0] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)xo, 0));
-                    H[1] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)(xo + (TY + 1) * 4096u), 0));
+                    Hl[0] = load16<double>(rx, (int)lane_b, xo);
+                    Hl[1] = load16<double>(rx, (int)lane_b, xo + (TY + 1) * PL_LINE_B);
                 }
 #pragma unroll
                 for (int l = 0; l < TY; ++l) {
-                    P[l] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)(xo + plane_b32 + (l + 1) * 4096u), 0));
-                    E[l] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rx, edge_b + 8, (int)(xo + (l + 1) * 4096u - 8u), 0));
+                    P[l] = load16<double>(rx, (int)lane_b, xo + plane_b32 + (l + 1) * PL_LINE_B);
+                    E[l] = load_edge<double>(rx, edge_b + 8, xo + (l + 1) * PL_LINE_B - 8u);
                 }
                 xo += plane_b32; yo += plane_b32; ++z;
             };
-            for (int g = run >> 2; g > 0; --g) {
-                fast_step(Cs[0], Cs[1], Cs[2], Hs[0], Es[0]);
-                fast_step(Cs[1], Cs[2], Cs[3], Hs[1], Es[1]);
-                fast_step(Cs[2], Cs[3], Cs[0], Hs[0], Es[0]);
-                fast_step(Cs[3], Cs[0], Cs[1], Hs[1], Es[1]);
-            }
+            for (int g = run >> 2; g > 0; --g) fast_group(fast_step, Cs, Hs, Es);
             if (run == 64) continue;                                      // look again: the run may go on
         }
         if (z >= zend) break;
         // ---- a slow step: a line needs another block decoded, the last planes (clamped requests), the ragged last plane, what
-        // a run leaves over after its groups of four; names rotated by copies ----
+        // a run leaves over after its groups of four ----
 #pragma unroll
         for (int l = 0; l < TY; ++l) {
             const int li = z * ny + (y0 + l);
             if (li < yline_hi) {                                          // uniform
-                PLANE_XS(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l)
-                double s0 = 0.0, s1 = 0.0;
+                double xs[2][7], s[2] = {};
+                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
                 const int blk = __builtin_amdgcn_readfirstlane(blocks[li]);
-                if (blk == hot) { PLANE_HOT_SUMS(s0, s1) }
+                if (blk == hot) hot_sums(s, aH, mH, xs);
                 else {
                     if (blk != other) { bitsO = decode(blk); other = blk; }
-                    PLANE_OTHER_SUMS(s0, s1)
+                    other_sums(s, s_other, t, bitsO, xs);
                 }
-                d2 o; o.x = alpha * s0; o.y = alpha * s1;
-                if (ZM == 1) { o.x = beta * Yo[l].x + o.x; o.y = beta * Yo[l].y + o.y; }
-                if (ZM == 2) { o.x = beta * c.x + o.x; o.y = beta * c.y + o.y; }
+                const d2 o = add_addend<ZM>(alpha, s, beta, Yo[l], Cs[1][l]);
                 __builtin_nontemporal_store(o, reinterpret_cast<d2 *>(reinterpret_cast<char *>(y + (long long)li * PL_ROWS) + lane_b));
             }
         }
-#pragma unroll
-        for (int l = 0; l < TY; ++l) {
-            Cs[0][l] = Cs[1][l]; Cs[1][l] = Cs[2][l]; Cs[2][l] = Cs[3][l]; Cs[3][l] = ld(z + 3, l + 1);
-            Es[0][l] = Es[1][l]; Es[1][l] = edge(z + 2, l + 1);
-            if (ZM == 1) Yo[l] = yold(z + 1, l);
-        }
-#pragma unroll
-        for (int l = 0; l < 2; ++l) { Hs[0][l] = Hs[1][l]; if constexpr (!FLAT) Hs[1][l] = ld(z + 2, (TY + 1) * l); }
+        rotate_by_copy<ZM>(Cs, Hs, Es, Yo, z, !FLAT, ld, edge, yold);
         ++z;
     }
     }       // pass
@@ -459,9 +369,6 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
             d[0] = dbg_t0; d[1] = dbg_flag; d[2] = dbg_data; d[3] = wall_clock64(); d[4] = (unsigned long long)(second ? z2 : z_first0); d[5] = (unsigned long long)(second ? mid_end : zend);
         }
     }
-#undef PLANE_XS
-#undef PLANE_HOT_SUMS
-#undef PLANE_OTHER_SUMS
 }
 
 #ifndef VEXHIP_HALO_WAVES
@@ -515,7 +422,7 @@ namespace vexhip {
 int plane_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, const double *zs, double beta, int64_t w, const void *pool,
         const int32_t *blocks, const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane)
 {
-    if (int rc = plane_check(plane, 0, 4096, n, w, pool && blocks && deltas && values, x, y, true)) return rc;      // the plan's tile, the plan's depth
+    if (int rc = plane_check(plane, 0, PL_LINE_B, n, w, pool && blocks && deltas && values, x, y, true)) return rc;      // the plan's tile, the plan's depth
     VEXHIP_REQUIRE(zm == 0 || zm == 2 || (zm == 1 && zs && (reinterpret_cast<uintptr_t>(zs) & 15) == 0), "plane product: the addend must be a 16-byte aligned vector");
     VEXHIP_SET_DEVICE(dev);
     const plane_dev pd = plane_launch(*plane, n, w, plane->tile, plane->depth);
@@ -578,8 +485,8 @@ static bool plane_geometry_with(long long cus, long long ny, long long nz, int h
     long long depth = depth_for(tile);
     if (const char *e = env(ENV_VEXHIP_PLANE_DEPTH)) depth = std::max(1, std::atoi(e));
     depth = std::min(depth, nz);
-    while ((depth + 4) * ny * 4096 >= (1ll << 32) && depth > 8) depth = (depth + 1) / 2;      // 32-bit byte offsets inside a workgroup's walk
-    if ((depth + 4) * ny * 4096 >= (1ll << 32)) return false;
+    while ((depth + 4) * ny * PL_LINE_B >= (1ll << 32) && depth > 8) depth = (depth + 1) / 2;      // 32-bit byte offsets inside a workgroup's walk
+    if ((depth + 4) * ny * PL_LINE_B >= (1ll << 32)) return false;
     out->lines_per_plane = (int32_t)ny; out->planes = (int32_t)nz; out->depth = (int32_t)depth; out->hot_block = hot; out->tile = (int32_t)tile;
     // cache policy of the y stores (launch.hpp with_launch_forms: the policies and their measurements); VEXHIP_PLANE_STORE overrides
     out->store_policy = tile == 4 ? 2 : 1;
@@ -616,7 +523,7 @@ int plane_apply_halo(int dev, hipStream_t s, int64_t n_ext, double alpha, int ap
         const int32_t *deltas, const double *values, const double *x, double *y, const vexhip_plane *plane, halo_dev H)
 {
     // (the kernel of the step is the one for tiles of two lines whatever the plan's tile; the depth checked is the plan's, the one walked is chosen below)
-    if (int rc = plane_check(plane, 2, 4096, n_ext, w, pool && blocks && deltas && values, x, y, true)) return rc;
+    if (int rc = plane_check(plane, 2, PL_LINE_B, n_ext, w, pool && blocks && deltas && values, x, y, true)) return rc;
     if (int rc = check_halo_step(H, plane->planes, (long long)plane->lines_per_plane * PL_ROWS, false)) return rc;
     VEXHIP_SET_DEVICE(dev);
     const int nzr = H.z1 - H.z0;

@@ -11,7 +11,7 @@
 // (spmat/csr.inl:163-170) in fp32.  Compiled with -ffp-contract=off.
 #include "common.hpp"
 #include "halo.hpp"
-#include "lanes.hpp"
+#include "walk.hpp"
 #include "plane.hpp"
 #include "storage.hpp"
 
@@ -79,21 +79,8 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
     // ---- a dictionary block -> values (into s_other) and validity (returned) of this lane's four rows at the seven positions ----
     const int wp = (pd.w + 1) >> 1;
     auto decode = [&](int blk) -> unsigned {
-        if (pd.pitch > 0) {                      // the matrix stored by grid line (grid.hip): a value code per position and row, 255 = no entry
-            const char *tb = pool + (long long)blk * 7 * pd.pitch + 4 * t;
-            unsigned bits = 0;
-#pragma unroll
-            for (int p = 0; p < 7; ++p) {
-                const unsigned c4 = *reinterpret_cast<const unsigned *>(tb + (long long)p * pd.pitch);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const unsigned code = (c4 >> (8 * r)) & 255u;
-                    s_other[4 * p + r][t] = s_value[code];            // entry 255 of the value table is 0.0
-                    bits |= (code != 255u ? 1u : 0u) << (4 * p + r);
-                }
-            }
-            return bits;
-        }
+        // the matrix stored by grid line (grid.hip): a value code per position and row, 255 = no entry
+        if (pd.pitch > 0) return decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 4 * t, pd.pitch, s_value, s_other, t);
         // a code block: per pair of ELL columns 256 words of diagonal codes, then as many of value codes; word i holds rows 2i, 2i + 1
         const unsigned *cw = reinterpret_cast<const unsigned *>(pool + (long long)blk * ((long long)wp * 2048)) + 2 * t;
         unsigned dcw[4][2], vcw[4][2];
@@ -127,16 +114,7 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
     unsigned long long mH[7][4];                // ... and the lanes with an entry, per position and row.  (56 scalar registers: the
     // compiler keeps some of them in lanes of vector registers, 40 v_readlane per line.  Measured at 512^3: these masks 0.2066 ms,
     // the lane's own 28 validity bits in a vector register 0.2085, NO masks at all 0.2035 -- the product is not bound by them.)
-    {
-        const unsigned bitsH = decode(hot);
-#pragma unroll
-        for (int p = 0; p < 7; ++p)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                aH[p][r] = s_other[4 * p + r][t];
-                mH[p][r] = __builtin_amdgcn_ballot_w64((bitsH >> (4 * p + r)) & 1u);
-            }
-    }
+    take_hot(decode(hot), s_other, t, aH, mH);
     unsigned bitsO = 0;
     int other = -1;                             // what s_other holds now is the hot block's: never asked for
 
@@ -180,11 +158,7 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
         return *reinterpret_cast<const f4u *>(reinterpret_cast<const char *>(zs + (long long)li * PL_ROWS) + lane_b);
     };
 
-    // ---- state at the top of the step for plane z: as in plane.hip ----
-    // Cs[0..3]: the tile's two centre lines in planes z-1, z, z+1, z+2;  Hs[0..1]: the halo lines (above, below) in planes z, z+1;
-    // Es[0..1]: per centre line the edge element of this lane in planes z, z+1.  A step consumes plane z-1's centres and plane
-    // z's halos and edges and requests into the SAME registers what plays that role three (centres) or two planes later; the
-    // fast loop runs groups of four steps with the names rotated.
+    // ---- the registers of the walk (walk.hpp), filled for plane z ----
     f4 Cs[4][TY], Hs[2][2], Yo[TY];
     float Es[2][TY];
     const unsigned plane_b32 = (unsigned)ny * (unsigned)P32_LINE_B;    // bytes from a line to the same line of the next plane
@@ -193,26 +167,7 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
         const_cast<float *>(x + ((long long)z_first * ny + (y0 - 1)) * PL_ROWS), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ZM == 1 ? zs : x) + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
-#pragma unroll
-    for (int l = 0; l < TY; ++l) { Cs[0][l] = ld(z - 1, l + 1); Cs[1][l] = ld(z, l + 1); Cs[2][l] = ld(z + 1, l + 1); Cs[3][l] = ld(z + 2, l + 1); }
-    Hs[0][0] = ld(z, 0); Hs[0][1] = ld(z, TY + 1); Hs[1][0] = ld(z + 1, 0); Hs[1][1] = ld(z + 1, TY + 1);
-#pragma unroll
-    for (int l = 0; l < TY; ++l) {
-        Es[0][l] = edge(z, l + 1); Es[1][l] = edge(z + 1, l + 1);
-        if (ZM == 1) Yo[l] = yold(z, l);
-    }
-
-    // x at the seven positions {-far, -512, -1, 0, +1, +512, +far} of the lane's four rows of tile line l
-#define P32_XS(P, C, N, H, E, l)                                                                                                     \
-        const f4 c = C[l], up = (l) == 0 ? H[0] : C[0], dn = (l) == TY - 1 ? H[1] : C[TY - 1], pv = P[l], nv = N[l];                     \
-        const float xs[4][7] = {{pv.x, up.x, shift_from_lower_lane(c.w, E[l]), c.x, c.y, dn.x, nv.x},                                 \
-                                {pv.y, up.y, c.x, c.y, c.z, dn.y, nv.y},                                                              \
-                                {pv.z, up.z, c.y, c.z, c.w, dn.z, nv.z},                                                              \
-                                {pv.w, up.w, c.z, c.w, shift_from_upper_lane(c.x, E[l]), dn.w, nv.w}};
-#define P32_HOT_SUMS(s)                                                                                                              \
-        _Pragma("unroll") for (int p = 0; p < 7; ++p) _Pragma("unroll") for (int r = 0; r < 4; ++r) s[r] += aH[p][r] * keep_lanes(xs[r][p], mH[p][r]);
-#define P32_OTHER_SUMS(s)                                                                                                            \
-        _Pragma("unroll") for (int p = 0; p < 7; ++p) _Pragma("unroll") for (int r = 0; r < 4; ++r) s[r] += s_other[4 * p + r][t] * keep_bit(xs[r][p], bitsO, 4 * p + r);
+    fill_registers<ZM>(Cs, Hs, Es, Yo, z, true, ld, edge, yold);
 
     // fast steps need nothing clamped: planes up to z + 3 inside x, both lines inside y
     int zh = zend;
@@ -223,96 +178,62 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
     }
 
     while (z < zend) {
-        // ---- how many of the next planes (<= 64) can take fast steps: both lines use the hot block or the other block ----
-        unsigned long long use_hot[TY];          // bit k: line l of plane z + k uses the hot block (else: the other block)
-        int run;
-        {
-            const int k = t & 63, zz = z + k;
-            const bool in = zz < zh;
-            bool ok = in;
-#pragma unroll
-            for (int l = 0; l < TY; ++l) {
-                const int bk = in ? blocks[(long long)zz * ny + (y0 + l)] : hot;
-                ok = ok && (bk == hot || bk == other);
-                use_hot[l] = __builtin_amdgcn_ballot_w64(bk == hot);
-            }
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-            run = ~m ? __builtin_ctzll(~m) : 64;
-        }
+        unsigned long long use_hot[TY];
+        const int run = fast_run(blocks, ny, y0, TY, z, zh, hot, other, t, use_hot);
         if (run >= 4) {
             // xo: plane z + 2, the line above the tile; yo: plane z, the tile's first line; both relative to the workgroup's first plane
             unsigned xo = (unsigned)((z + 2 - z_first) * plane_b32), yo = (unsigned)((z - z_first) * plane_b32);
-            auto fast_step = [&](f4 (&P)[TY], f4 (&C)[TY], f4 (&N)[TY], f4 (&H)[2], float (&E)[TY]) {
+            auto fast_step = [&](f4 (&P)[TY], f4 (&C)[TY], f4 (&N)[TY], f4 (&Hl)[2], float (&E)[TY]) {
                 f4 o[TY];
 #pragma unroll
                 for (int l = 0; l < TY; ++l) {
-                    P32_XS(P, C, N, H, E, l)
-                    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (use_hot[l] & 1ull) { P32_HOT_SUMS(s) } else { P32_OTHER_SUMS(s) }      // uniform
-                    o[l].x = alpha * s[0]; o[l].y = alpha * s[1]; o[l].z = alpha * s[2]; o[l].w = alpha * s[3];
-                    if (ZM == 1) o[l] = beta * Yo[l] + o[l];
-                    if (ZM == 2) o[l] = beta * c + o[l];
+                    float xs[4][7], s[4] = {};
+                    stencil_x(P, C, N, Hl, E, l, xs);
+                    if (use_hot[l] & 1ull) hot_sums(s, aH, mH, xs); else other_sums(s, s_other, t, bitsO, xs);      // uniform
+                    o[l] = add_addend<ZM>(alpha, s, beta, Yo[l], C[l]);
                 }
 #pragma unroll
                 for (int l = 0; l < TY; ++l) use_hot[l] >>= 1;
 #pragma unroll
-                for (int l = 0; l < TY; ++l)       // written once, not read again by this kernel
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, o[l]), ry, (int)lane_b, (int)(yo + l * (unsigned)P32_LINE_B), STORE_AUX);
+                for (int l = 0; l < TY; ++l) store16<STORE_AUX>(o[l], ry, (int)lane_b, yo + l * P32_LINE_B);       // written once, not read again by this kernel
                 if (ZM == 1) {
 #pragma unroll
-                    for (int l = 0; l < TY; ++l) Yo[l] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rz, (int)lane_b, (int)(yo + plane_b32 + l * (unsigned)P32_LINE_B), 0));
+                    for (int l = 0; l < TY; ++l) Yo[l] = load16<float>(rz, (int)lane_b, yo + plane_b32 + l * P32_LINE_B);
                 }
-                H[0] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)xo, 0));
-                H[1] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)(xo + (TY + 1) * (unsigned)P32_LINE_B), 0));
+                Hl[0] = load16<float>(rx, (int)lane_b, xo);
+                Hl[1] = load16<float>(rx, (int)lane_b, xo + (TY + 1) * P32_LINE_B);
 #pragma unroll
                 for (int l = 0; l < TY; ++l) {
-                    P[l] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)lane_b, (int)(xo + plane_b32 + (l + 1) * (unsigned)P32_LINE_B), 0));
-                    E[l] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, edge_b + 4, (int)(xo + (l + 1) * (unsigned)P32_LINE_B - 4u), 0));
+                    P[l] = load16<float>(rx, (int)lane_b, xo + plane_b32 + (l + 1) * P32_LINE_B);
+                    E[l] = load_edge<float>(rx, edge_b + 4, xo + (l + 1) * P32_LINE_B - 4u);
                 }
                 xo += plane_b32; yo += plane_b32; ++z;
             };
-            for (int g = run >> 2; g > 0; --g) {
-                fast_step(Cs[0], Cs[1], Cs[2], Hs[0], Es[0]);
-                fast_step(Cs[1], Cs[2], Cs[3], Hs[1], Es[1]);
-                fast_step(Cs[2], Cs[3], Cs[0], Hs[0], Es[0]);
-                fast_step(Cs[3], Cs[0], Cs[1], Hs[1], Es[1]);
-            }
+            for (int g = run >> 2; g > 0; --g) fast_group(fast_step, Cs, Hs, Es);
             if (run == 64) continue;                                      // look again: the run may go on
         }
         if (z >= zend) break;
         // ---- a slow step: a line needs another block decoded, the last planes (clamped requests), the ragged last plane, what
-        // a run leaves over after its groups of four; names rotated by copies ----
+        // a run leaves over after its groups of four ----
 #pragma unroll
         for (int l = 0; l < TY; ++l) {
             const int li = z * ny + (y0 + l);
             if (li < nslices) {                                           // uniform
-                P32_XS(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l)
-                float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                float xs[4][7], s[4] = {};
+                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
                 const int blk = __builtin_amdgcn_readfirstlane(blocks[li]);
-                if (blk == hot) { P32_HOT_SUMS(s) }
+                if (blk == hot) hot_sums(s, aH, mH, xs);
                 else {
                     if (blk != other) { bitsO = decode(blk); other = blk; }
-                    P32_OTHER_SUMS(s)
+                    other_sums(s, s_other, t, bitsO, xs);
                 }
-                f4 o; o.x = alpha * s[0]; o.y = alpha * s[1]; o.z = alpha * s[2]; o.w = alpha * s[3];
-                if (ZM == 1) o = beta * Yo[l] + o;
-                if (ZM == 2) o = beta * c + o;
+                const f4 o = add_addend<ZM>(alpha, s, beta, Yo[l], Cs[1][l]);
                 *reinterpret_cast<f4u *>(reinterpret_cast<char *>(y + (long long)li * PL_ROWS) + lane_b) = o;
             }
         }
-#pragma unroll
-        for (int l = 0; l < TY; ++l) {
-            Cs[0][l] = Cs[1][l]; Cs[1][l] = Cs[2][l]; Cs[2][l] = Cs[3][l]; Cs[3][l] = ld(z + 3, l + 1);
-            Es[0][l] = Es[1][l]; Es[1][l] = edge(z + 2, l + 1);
-            if (ZM == 1) Yo[l] = yold(z + 1, l);
-        }
-#pragma unroll
-        for (int l = 0; l < 2; ++l) { Hs[0][l] = Hs[1][l]; Hs[1][l] = ld(z + 2, (TY + 1) * l); }
+        rotate_by_copy<ZM>(Cs, Hs, Es, Yo, z, true, ld, edge, yold);
         ++z;
     }
-#undef P32_XS
-#undef P32_HOT_SUMS
-#undef P32_OTHER_SUMS
 }
 
 template <int ZM, int STORE_AUX, bool HALO = false>
