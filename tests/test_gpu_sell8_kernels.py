@@ -21,6 +21,17 @@ What runs where
     reference of every march test.)
   * test_march_*: `vexhip_sell8_march_plan` against `march_plan_host`, its declines, and `vexhip_spmv_sell8v_march_*`
     (`sell8_march_kernel<W>`, W = 1, 2, 3, 7, 8) with `run` written into the plan.
+  * test_halo_*: `sell8_pair_halo_kernel<double, W, VCODED, DICT>`, the pair product as one device's whole product step, alone in one
+    process: `vexhip_spmat_create_f64_i32` with the storage pinned (SELL8 / SELL8V, no march, plane or grid plan, with and without
+    a slice dictionary; checked from `vexhip_spmat_get_info` and against the encoders) on a stored strip as
+    `vexcl_amd.distributed.halo_extended_csr` builds it (`Strip`, `strip_matrix`), `vexhip_dist_spmv_create_halo_pull` without a window
+    and with VEXHIP_PULL_EVENTS -- no flag is raised or waited for; a VEXHIP_PULL_FLAGS plan would wait for a flag nobody raises and
+    is never created here --, `vexhip_dist_spmv_apply_pull` with x and the two ghost ranges as three canaried device arrays.  All 32
+    instantiations (widths 1..8, both value forms, streamed and from a dictionary); strips with one, two and three edge slices per
+    side, shorter than two reaches, with a neighbour on one side only and with none; the +-1 diagonals across both seams inside one
+    lane; reach equal to the ghost range; three products on one plan with the vectors rewritten in place.  The expected bits are
+    `oracle.spmv_csr` on the stored matrix with x_ext = [x_below | x | x_above], own rows; without a neighbour also
+    `vexhip_spmat_apply_f64` of the same handle.
   * test_generators_encoders_and_host_models (no GPU): pins everything the GPU tests take for granted.
 The module has no `pytestmark`: the last test has to run without a GPU, so every GPU test carries the `gpu` mark itself.
 
@@ -45,15 +56,18 @@ Canaries
   the largest column of the matrix); every element of x that no entry references is NaN, and so is everything behind x_last.  y has 64
   sentinel elements on either side, compared as bytes after every call; before a `=` call y itself holds the sentinel, so a slice that
   no workgroup visits shows.  Filled buffers, tables, dictionaries sit between guards of 64 elements.  All of these addresses lie
-  inside live allocations.
+  inside live allocations.  The halo tests keep x (exactly the own rows) and each ghost range (exactly `halo` elements, 16-byte
+  aligned) in NaN-filled tensors of their own; after every plan `timed_out` is 0.
 
 Launch geometry
   No product is launched before `visit_once` has shown on the host that its geometry -- the traversal (`strip_visits`, a restatement
   of traversal.hpp `traversal_slice`) and, for the march product, the traversal together with `run` (`march_visits`, a restatement
-  of sell8.hip `march_run`) -- visits every slice exactly once and that every other place is a hole.
+  of sell8.hip `march_run`) -- visits every slice exactly once and that every other place is a hole.  For the halo role
+  `halo_geometry` shows the same of `halo_visits` (the kernel's inner / lower edge / upper edge order and its short-strip rule), and
+  that no workgroup reads a ghost range it is not told to need.
 
 Left out
-  `sell8_pair_halo_kernel` (tests/test_gpu_distributed.py), `sell8v_runs_*` (reachable through vexhip_spmat only), spmm.hip; the plane
+  `sell8v_runs_*` (reachable through vexhip_spmat only), spmm.hip; the flags of the halo role (tests/test_gpu_distributed.py); the plane
   and grid products and their plans have a file of their own, tests/test_gpu_plane_grid_kernels.py.  The `_dict` products with
   explicit maps, and `sell8_pair_kernel<W, *, true>` at the widths not named above.
   The march plan looks at diagonals and slice numbers only: that a SELL8 matrix (stored values) is not given to
@@ -593,12 +607,12 @@ def segment_sums(a, ptr):
 
 
 class Case:
-    def __init__(self, oracle, mat, dtype, scheme):
+    def __init__(self, oracle, mat, dtype, scheme, salt=0):
         self.mat, self.dtype, self.scheme = mat, dtype, scheme
         ptr, col, val = mat.csr(dtype, scheme)
         used = np.zeros(mat.m, dtype=bool)
         used[col] = True
-        seed = 1000 + 17 * mat.n + 3 * mat.m + len(mat.col) % 1000
+        seed = 1000 + 17 * mat.n + 3 * mat.m + len(mat.col) % 1000 + 7919 * salt    # salt: further vectors for the same matrix
         self.x = (oracle.random_f64(seed, mat.m) - 0.5).astype(dtype)
         tiny = (val != 0) & (np.abs(val) < np.finfo(dtype).tiny)
         self.x[col[tiny]] = np.copysign(dtype(0.25), self.x[col[tiny]])   # a subnormal value meets a power of two: its product is exact (the bound assumes no underflow)
@@ -632,11 +646,166 @@ class Case:
 _CASES = {}
 
 
-def case_of(oracle, mat, dtype, scheme):
-    key = (mat.name, np.dtype(dtype).name, scheme)
+def case_of(oracle, mat, dtype, scheme, salt=0):
+    key = (mat.name, np.dtype(dtype).name, scheme) + ((salt,) if salt else ())
     if key not in _CASES:
-        _CASES[key] = Case(oracle, mat, dtype, scheme)
+        _CASES[key] = Case(oracle, mat, dtype, scheme, salt)
     return _CASES[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the halo role of the pair product: stored strips, their matrices, the kernel's block-to-slice mapping
+# ---------------------------------------------------------------------------------------------------------------------------
+class Strip:
+    """One device's strip as vexcl_amd.distributed.halo_extended_csr stores it: `lo` empty rows in front of the own rows where there
+    is a lower neighbour, `hi` empty rows behind them where there is an upper one (a ghost range of `halo` rows each), columns counted
+    from the first element of the lower ghost range.  reach: the largest |diagonal| of its matrices."""
+
+    def __init__(self, name, halo, rows, lower, upper, reach):
+        self.name, self.halo, self.rows, self.lower, self.upper, self.reach = name, halo, rows, lower, upper, reach
+        self.lo, self.hi = halo * lower, halo * upper
+        self.n = self.lo + rows + self.hi                               # rows (and columns) of the stored matrix
+        self.ns, self.edge = rows // SLICE, (reach + SLICE - 1) // SLICE
+        assert rows % SLICE == 0 and halo % SLICE == 0 and rows % halo == 0 and 0 < reach <= halo
+
+    def own(self, a):
+        return a[self.lo:self.lo + self.rows]
+
+
+STRIPS = {s.name: s for s in (
+    Strip("seams", 512, 4 * 512, True, True, 1),                      # the +-1 diagonals straddle both seams inside one lane
+    Strip("reach_is_halo", 512, 4 * 512, True, True, 512),            # pairs of the inner slices end at the last own element; the ghost ranges' first and last elements
+    Strip("edge2", 1024, 4 * 1024, True, True, 513),                  # two edge slices per side, four inner ones
+    Strip("short513", 1024, 1024, True, True, 513),                   # ns < 2 edge: every slice needs both ghost ranges
+    Strip("short1024", 1024, 1024, True, True, 1024),
+    Strip("edge3", 1536, 1536, True, True, 1025),                     # edge = ns = 3
+    Strip("lower", 512, 4 * 512, True, False, 512),                   # x and y moved by the lower ghost range
+    Strip("upper", 512, 4 * 512, False, True, 512),                   # ... and not moved
+    Strip("alone", 512, 4 * 512, False, False, 512),                  # every slice inner: the plain pair product
+    Strip("dict", 512, 64 * 512, True, True, 512),                    # 66 stored slices that repeat: the DICT forms
+)}
+HALO_FAMILIES = ("bands", "holes", "crossed")
+PULL_EVENTS = 2                                                       # VEXHIP_PULL_EVENTS (include/vexhip.h): the only order a one-process test may ask for
+HALO_EXPECT = {                                                       # per workgroup: (own slice, needs the lower, the upper ghost range)
+    "seams": [(1, False, False), (2, False, False), (0, True, False), (3, False, True)],
+    "reach_is_halo": [(1, False, False), (2, False, False), (0, True, False), (3, False, True)],
+    "edge2": [(2, False, False), (3, False, False), (4, False, False), (5, False, False), (0, True, False), (1, True, False), (6, False, True), (7, False, True)],
+    "short513": [(0, True, True), (1, True, True)],
+    "short1024": [(0, True, True), (1, True, True)],
+    "edge3": [(0, True, True), (1, True, True), (2, True, True)],
+    "lower": [(1, False, False), (2, False, False), (3, False, False), (0, True, False)],
+    "upper": [(0, False, False), (1, False, False), (2, False, False), (3, False, True)],
+    "alone": [(0, False, False), (1, False, False), (2, False, False), (3, False, False)],
+    "dict": [(s, False, False) for s in range(1, 63)] + [(0, True, False), (63, False, True)],
+}
+
+
+def halo_visits(ns, edge, has_lo, has_hi):
+    """sell8.hip sell8_pair_halo_kernel, workgroup -> (own slice, need_lo, need_hi): the inner slices first, then the lower edge, then
+    the upper edge; in a strip shorter than two reaches a slice may need both ghost ranges."""
+    elo = min(edge, ns) if has_lo else 0
+    ehi = min(edge, ns - elo) if has_hi else 0
+    inner = ns - elo - ehi
+    out = []
+    for b in range(ns):
+        need_lo = need_hi = False
+        if b < inner:
+            so = b + elo
+        elif b < inner + elo:
+            so, need_lo = b - inner, True
+        else:
+            so, need_hi = ns - ehi + (b - inner - elo), True
+        if has_lo and has_hi and ns < 2 * edge:
+            need_lo, need_hi = need_lo or so < edge, need_hi or so >= ns - edge
+        out.append((so, need_lo, need_hi))
+    return out
+
+
+def halo_diagonals(fam, w, reach):
+    """(diagonals of the even rows, of the odd rows), ascending, the largest magnitude `reach`.  crossed: the odd rows' are the even
+    rows' + 2 -- disjoint sets, so a pair's merged list exceeds w."""
+    if reach == 1:
+        assert w <= (1 if fam == "crossed" else 3)
+        return (np.array([-1]), np.array([1])) if fam == "crossed" else (np.sort([-1, 1, 0][:w]),) * 2
+    assert reach >= 16
+    if fam == "crossed":
+        even = np.sort([-reach, reach - 2, 0, -4, 4, -8, 8, 12][:w])
+        return even, even + 2
+    return (np.sort([-reach, reach, 0, -1, 1, -3, 3, 6][:w]),) * 2
+
+
+def strip_matrix(oracle, strip, fam, w):
+    """The stored matrix of a strip, one of three of the file's families with the strip's reach.  bands: every own row holds the w
+    diagonals (pairs on one diagonal).  holes: every third row keeps a diagonal with probability 0.8, the same rows in every slice
+    (255 / 254 beside an entry; more than a third of all stored rows stay full: no CSR tail).  crossed: in two pairs of three the odd
+    row holds other diagonals than the even one (plain packing: two diagonals in one lane).  The ghost rows are empty; a diagonal
+    that leaves the stored columns (no neighbour on that side) is cut."""
+    name = "strip_%s_%s_w%d" % (strip.name, fam, w)
+
+    def make():
+        i = np.arange(strip.n, dtype=np.int64)
+        even, odd = halo_diagonals(fam, w, strip.reach)
+        D = np.where((((i // 2) % 3 != 0) & (i % 2 == 1))[:, None], odd[None, :], even[None, :])
+        keep = np.ones((SLICE, w), dtype=bool)
+        if fam == "holes":
+            keep = oracle.random_f64(5000 + 31 * w, SLICE * w).reshape(SLICE, w) < 0.8
+            keep[np.arange(SLICE) % 3 != 0] = True
+        own = (i >= strip.lo) & (i < strip.lo + strip.rows)
+        return assemble(oracle, name, strip.n, D, keep[i % SLICE] & own[:, None], strip.n)
+    return _cached(name, make)
+
+
+def halo_schemes(kind, use_dict):
+    """The value scheme of a strip's matrix: stored values are random; value codes take seven values, or -- where the slices
+    have to repeat -- one value per diagonal."""
+    return "random" if kind == "sell8" else "diag5" if use_dict else "hash7"
+
+
+def halo_families(strip, w):
+    """The families a strip is tested with at width w: `holes` only where the own rows are more than half of the stored ones (the
+    hybrid-ELL rule takes the full width while a third of ALL stored rows are full; fewer, and the rows with holes make a CSR tail),
+    `crossed` at reach 1 only with one column."""
+    fams = [f for f in HALO_FAMILIES if not (f == "holes" and 2 * strip.rows < strip.n)]
+    return [f for f in fams if not (f == "crossed" and strip.reach == 1 and w > 1)]
+
+
+def halo_cases():
+    """(strip, ELL width, slice dictionary) of every GPU test of the halo role."""
+    out = [(STRIPS["edge2"], w, False) for w in range(1, 9)] + [(STRIPS["dict"], w, True) for w in range(1, 9)]
+    out += [(STRIPS["seams"], 3, False), (STRIPS["seams"], 1, False)]
+    return out + [(s, 7, False) for name, s in STRIPS.items() if name not in ("seams", "edge2", "dict")]
+
+
+def gather_kinds(codes, slices):
+    """Per lane and ELL column of the given stored slices, from the codes (rows x w): (both rows on one diagonal, padding beside
+    an entry, two different diagonals) -- the three ways through gather_pair that load something."""
+    rows = (np.asarray(slices, dtype=np.int64)[:, None] * SLICE + np.arange(0, SLICE, 2)[None, :]).reshape(-1)
+    c0, c1 = codes[rows].astype(np.int64), codes[rows + 1].astype(np.int64)
+    m0, m1 = c0 < PAD_UNSAFE, c1 < PAD_UNSAFE
+    return int(np.count_nonzero(m0 & m1 & (c0 == c1))), int(np.count_nonzero(m0 ^ m1)), int(np.count_nonzero(m0 & m1 & (c0 != c1)))
+
+
+def halo_geometry(strip, mat):
+    """The launch of a strip's product restated and checked on the host -- no product is launched before this has passed: every own
+    slice exactly once; a workgroup reads a ghost range only where `halo_visits` says so (anything else would leave x); the inner
+    slices stay inside the own range even with their 16-byte pairs.  Returns the inner slices in stored numbering."""
+    visits = halo_visits(strip.ns, strip.edge, strip.lower, strip.upper)
+    assert visit_once([so for so, _, _ in visits], strip.ns), (strip.name, "not every own slice once: no launch")
+    first, last = np.full(strip.n // SLICE, strip.n, dtype=np.int64), np.full(strip.n // SLICE, -1, dtype=np.int64)
+    np.minimum.at(first, mat.rows // SLICE, mat.col)
+    np.maximum.at(last, mat.rows // SLICE, mat.col)
+    inner = []
+    for so, need_lo, need_hi in visits:
+        sl = so + strip.lo // SLICE
+        assert (need_lo or first[sl] >= strip.lo) and (need_hi or last[sl] < strip.lo + strip.rows), (strip.name, so, "reads a ghost range it does not wait for")
+        assert not (need_lo and not strip.lower) and not (need_hi and not strip.upper), (strip.name, so)
+        if not (need_lo or need_hi):
+            # a pair is x[i + d], x[i + d + 1] of the lane's even row i: beside a ghost range it must stay inside the own range (where
+            # the stored x ends instead, the 254 codes keep it inside: the encoders' business)
+            assert not strip.lower or sl * SLICE - strip.reach >= strip.lo, (strip.name, so)
+            assert not strip.upper or sl * SLICE + SLICE - 1 + strip.reach < strip.lo + strip.rows, (strip.name, so)
+            inner.append(sl)
+    return inner
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1335,6 +1504,220 @@ def test_march_plan_declines_and_width_9_is_refused(G, oracle):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# 5. the halo role of the pair product, in one process
+# ---------------------------------------------------------------------------------------------------------------------------
+class HaloPlan:
+    """A strip's matrix as a vexhip_spmat in the storage the test names -- checked from vexhip_spmat_get_info and, where the handle
+    keeps its slices, byte for byte against the encoder -- and its pull plan without a window (VEXHIP_PULL_EVENTS: no flag is raised
+    or waited for, the launch is sell8_pair_halo_kernel alone)."""
+
+    def __init__(self, G, oracle, strip, mat, kind, w, use_dict):
+        from vexcl_amd import _capi
+        L = G.L
+        self.G, self.strip, self.mat, self.kind, self.w = G, strip, mat, kind, w
+        self.scheme = halo_schemes(kind, use_dict)
+        self.what = (strip.name, mat.name, kind, "width %d" % w, "dictionary" if use_dict else "streamed")
+        self.inner = halo_geometry(strip, mat)                          # before anything is launched
+        ptr, col, val = mat.csr(np.float64, self.scheme)
+        assert mat.n == strip.n and oracle.hell_width(ptr) == w == mat.lens.max(), self.what
+        self.csr = device_csr(G, ptr, col, val)
+        self.h, self.plan = ctypes.c_void_p(), ctypes.c_void_p()
+        flags = _capi.SPMAT_NO_MARCH | _capi.SPMAT_NO_PLANE | (0 if use_dict else _capi.SPMAT_NO_DICTIONARY)
+        L.spmat_create_f64_i32(0, G.stream(), mat.n, _vp(self.csr[0]), _vp(self.csr[1]), _vp(self.csr[2]),
+                               _capi.SPMAT_SELL8 if kind == "sell8" else _capi.SPMAT_SELL8V, flags, ctypes.byref(self.h))
+        try:
+            info = _capi.SpMatInfo()
+            L.spmat_get_info(self.h, ctypes.byref(info))
+            assert _capi.SPMAT_NAMES[info.format] == kind and info.tail_nnz == 0 and info.ell_width == w and info.rows == mat.n, self.what + (info.format, info.tail_nnz, info.ell_width)
+            assert (info.dictionary_blocks > 0) == use_dict and bool(info.slice_blocks) == use_dict, self.what + (info.dictionary_blocks,)
+            assert info.plane.usable == 0 and info.grid.usable == 0 and info.march.usable == 0, self.what
+            deltas, values, max_col = tables(ptr, col, val, w)
+            assert info.ndeltas == len(deltas) and np.abs(deltas).max() == strip.reach, self.what
+            self.codes = _coded(ptr, col, w, deltas, max_col, mat.slots(w))[2]
+            want = encode_sell8(ptr, col, val, w, deltas, max_col, np.float64, mat.slots(w)) if kind == "sell8" else \
+                encode_sell8v(ptr, col, val, w, deltas, max_col, np.float64, values, mat.slots(w))
+
+            def fetch(address, count, np_dtype):
+                got = np.empty(count, dtype=np_dtype)
+                L.memcpy_d2h(0, got.ctypes.data, address, got.nbytes, G.stream(), 1)
+                return got
+            if info.sell_bytes:                                         # (a value-coded matrix with a dictionary keeps its pool only)
+                assert info.sell_bytes == len(want) and fetch(info.sell, len(want), np.uint8).tobytes() == want.tobytes(), self.what + ("the stored slices are not the encoder's",)
+            else:
+                assert kind == "sell8v" and use_dict, self.what
+            if use_dict:                                                # the blocks in order of first appearance, as vexhip_slice_dictionary numbers them
+                ns, code_bytes = mat.n // SLICE, (w + 1) // 2 * (1024 if kind == "sell8" else 2048)
+                slices = want.reshape(ns, -1)[:, :code_bytes]
+                ids, reps = first_appearance(slices)
+                assert info.dictionary_blocks == len(reps) and np.array_equal(fetch(info.slice_blocks, ns, np.int32), ids), self.what + (info.dictionary_blocks, len(reps))
+                assert fetch(info.code_pool, len(reps) * code_bytes, np.uint8).tobytes() == slices[reps].tobytes(), self.what + ("the pool is not the encoder's",)
+            L.dist_spmv_create_halo_pull(None, self.h, strip.rows, strip.halo, 0 if strip.lower else -1, 1 if strip.upper else -1,
+                                         PULL_EVENTS, ctypes.byref(self.plan))
+        except BaseException:
+            self.close()
+            raise
+
+    def kinds(self):
+        """gather_kinds of the slices that take the inner gather."""
+        return gather_kinds(self.codes, self.inner)
+
+    def apply(self, x, y, alpha, append, below, above):
+        self.G.L.dist_spmv_apply_pull(self.plan, self.G.stream(), float(alpha), int(append), _vp(x), _vp(y), _vp(below), _vp(above))
+
+    def apply_plain(self, x, y, alpha, append):
+        self.G.L.spmat_apply_f64(self.h, self.G.stream(), float(alpha), int(append), _vp(x), _vp(y))
+
+    def timed_out(self):
+        t, transport, direct = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+        self.G.L.dist_spmv_status(self.plan, ctypes.byref(t), ctypes.byref(transport), ctypes.byref(direct))
+        return t.value
+
+    def close(self):
+        if self.plan:
+            self.G.L.dist_spmv_destroy(self.plan)
+        if self.h:
+            self.G.L.spmat_destroy(self.h)
+        self.plan, self.h = ctypes.c_void_p(), ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class HaloVectors:
+    """x, the two ghost ranges and y of a strip on the device.  x: exactly the own rows, at element 3 of a NaN-filled tensor; the
+    ghost ranges: exactly `halo` elements at element 2 (16-byte aligned, as apply_pull requires) of NaN-filled tensors of their own;
+    y between sentinels, off (y_offset = 1) or on a 16-byte boundary.  `load` rewrites all of them in place from a case of the
+    stored matrix: x_ext = [x_below | x | x_above], NaN wherever no entry reads."""
+
+    def __init__(self, G, strip, y_offset=1):
+        self.G, self.strip, self.y_at = G, strip, GUARD + y_offset
+
+        def canary(count, at):
+            whole = G.up(np.full(count + 8, np.nan))
+            assert (whole.data_ptr() + 8 * at) % 16 == 8 * (at % 2)
+            return whole, whole[at:at + count]
+        self.xbuf, self.x = canary(strip.rows, 3)
+        self.bbuf, self.below = canary(strip.halo, 2) if strip.lower else (None, None)
+        self.abuf, self.above = canary(strip.halo, 2) if strip.upper else (None, None)
+        self.ybuf = G.up(np.full(strip.rows + 2 * GUARD + 2, SENTINEL))
+        assert self.ybuf.data_ptr() % 16 == 0
+
+    def load(self, C):
+        s, up = self.strip, self.G.up
+        x_ext = np.full(s.n, np.nan)
+        x_ext[:len(C.x)] = C.x
+        for whole, at, part in ((self.xbuf, 3, s.own(x_ext)), (self.bbuf, 2, x_ext[:s.lo]), (self.abuf, 2, x_ext[s.lo + s.rows:])):
+            if whole is not None:
+                host = np.full(len(part) + 8, np.nan)
+                host[at:at + len(part)] = part
+                whole.copy_(up(host))
+        self.C, self.start = C, {}
+        for mode in MODES:
+            ybuf = np.full(s.rows + 2 * GUARD + 2, SENTINEL)
+            if mode[1]:
+                ybuf[self.y_at:self.y_at + s.rows] = s.own(C.y0)
+            self.start[mode] = ybuf
+
+    def run(self, P, mode, plain=False):
+        """One product in place; returns the whole y tensor on the host."""
+        self.ybuf.copy_(self.G.up(self.start[mode]))
+        y = self.ybuf[self.y_at:self.y_at + self.strip.rows]
+        if plain:
+            P.apply_plain(self.x, y, *mode)
+        else:
+            P.apply(self.x, y, *mode, self.below, self.above)
+        return self.ybuf.cpu().numpy()
+
+
+def check_halo(oracle, P, V, what):
+    """Both modes: every own row finite, the oracle's bits (its product on the stored matrix, own rows), within the derived bound;
+    every other byte of the y tensor unchanged; without a neighbour also the bytes of vexhip_spmat_apply_f64."""
+    s, C = P.strip, V.C
+    own = slice(V.y_at, V.y_at + s.rows)
+    for mode in MODES:
+        out, ref = V.run(P, mode), C.reference(oracle, mode)
+        got, want = out[own], s.own(ref)
+        assert np.all(np.isfinite(got)), what + (mode, "not finite: row %d" % np.flatnonzero(~np.isfinite(got))[0])
+        assert np.array_equal(got, want), what + (mode, first_difference(got, want))
+        whole = ref.copy()
+        whole[s.lo:s.lo + s.rows] = got
+        assert C.within_bound(whole, mode), what + (mode, "outside the bound of the high-precision reference")
+        rest = out.copy()
+        rest[own] = V.start[mode][own]
+        assert rest.tobytes() == V.start[mode].tobytes(), what + (mode, "a guard element changed")
+        if not (s.lower or s.upper):
+            assert V.run(P, mode, plain=True).tobytes() == out.tobytes(), what + (mode, "differs from vexhip_spmat_apply_f64")
+    assert P.timed_out() == 0, what
+
+
+def check_strip(G, oracle, strip, w, use_dict, kinds, y_offsets=(1,)):
+    """Every family of the strip at width w, in both value forms; returns the gather kinds of the inner slices, summed."""
+    seen = np.zeros(3, dtype=np.int64)
+    for fam in halo_families(strip, w):
+        mat = strip_matrix(oracle, strip, fam, w)
+        for kind in kinds:
+            with HaloPlan(G, oracle, strip, mat, kind, w, use_dict) as P:
+                for y_offset in y_offsets:
+                    V = HaloVectors(G, strip, y_offset)
+                    V.load(case_of(oracle, mat, np.float64, P.scheme))
+                    check_halo(oracle, P, V, P.what + ("y offset %d" % y_offset,))
+                k = np.array(P.kinds())
+                assert k[HALO_FAMILIES.index(fam)] > 0 or not P.inner, P.what + (k.tolist(), "the family no longer takes its way through the inner gather")
+                seen += k
+    return seen
+
+
+every_width = pytest.mark.parametrize("w", range(1, 9))
+both_forms = pytest.mark.parametrize("kind", ("sell8", "sell8v"))
+
+
+@gpu
+@every_width
+@both_forms
+def test_halo_every_width_streamed(G, oracle, w, kind):
+    """sell8_pair_halo_kernel<double, W, VCODED, false>, W = 1..8, on a strip with two edge slices per side and four inner ones
+    (reach 513 in ghost ranges of 1024): all three gathers in the inner slices, both ghost ranges through the translated access."""
+    seen = check_strip(G, oracle, STRIPS["edge2"], w, False, (kind,))
+    assert np.all(seen > 0), (w, kind, seen.tolist())
+
+
+@gpu
+@every_width
+@both_forms
+def test_halo_every_width_with_a_dictionary(G, oracle, w, kind):
+    """sell8_pair_halo_kernel<double, W, VCODED, true> on 66 stored slices whose code blocks repeat (ns >= 64, 4 blocks <= ns)."""
+    seen = check_strip(G, oracle, STRIPS["dict"], w, True, (kind,))
+    assert np.all(seen > 0), (w, kind, seen.tolist())
+
+
+@gpu
+@pytest.mark.parametrize("name", [n for n in STRIPS if n not in ("edge2", "dict")])
+def test_halo_geometries(G, oracle, name):
+    """The other strips at width 7 (reach 1: widths 3 and 1), y off and on a 16-byte boundary: the seams inside one lane, reach equal
+    to the ghost range, strips shorter than two reaches, a neighbour on one side only and none (then also against
+    vexhip_spmat_apply_f64)."""
+    strip = STRIPS[name]
+    seen = sum(check_strip(G, oracle, strip, w, False, ("sell8", "sell8v"), (1, 0)) for s, w, _ in halo_cases() if s is strip)
+    assert strip.ns < 2 * strip.edge or np.all(seen > 0), (name, seen.tolist())
+
+
+@gpu
+@both_forms
+def test_halo_repeated_products_on_one_plan(G, oracle, kind):
+    """Three products back to back on one plan, x and both ghost ranges rewritten in place in between."""
+    strip, w = STRIPS["reach_is_halo"], 7
+    mat = strip_matrix(oracle, strip, "holes", w)
+    with HaloPlan(G, oracle, strip, mat, kind, w, False) as P:
+        V = HaloVectors(G, strip)
+        for salt in (0, 1, 2):
+            V.load(case_of(oracle, mat, np.float64, P.scheme, salt))
+            check_halo(oracle, P, V, P.what + ("vectors %d" % salt,))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # the CPU test
 # ---------------------------------------------------------------------------------------------------------------------------
 def every_storage_case(oracle):
@@ -1494,6 +1877,52 @@ def test_generators_encoders_and_host_models(oracle):
             visited, runs = march_visits(ns, run)
             assert visit_once(visited, ns) and len(runs) == (ns + run - 1) // run and all(c > 0 for _, c in runs)
     assert not visit_once([0, 1, 1], 3) and not visit_once([0, 2, -1], 3) and not visit_once([0, 1, 2, 3], 3) and not visit_once([0, 1, 2, -2], 3)
+
+    # the halo role: the kernel's block-to-slice mapping against hand-written expectations, and every strip's matrices -- full
+    # width without a CSR tail, the intended reach, slices that repeat where a dictionary is wanted, every launch's geometry, and
+    # the three kinds of gather in the slices that take the inner gather
+    assert sorted(HALO_EXPECT) == sorted(STRIPS) and {s for s, _, _ in halo_cases()} == set(STRIPS.values())
+    for name, strip in STRIPS.items():
+        visits = halo_visits(strip.ns, strip.edge, strip.lower, strip.upper)
+        assert visits == HALO_EXPECT[name] and visit_once([so for so, _, _ in visits], strip.ns), name
+    assert halo_visits(5, 2, True, False) == [(2, False, False), (3, False, False), (4, False, False), (0, True, False), (1, True, False)]
+    assert halo_visits(3, 2, True, True) == [(0, True, False), (1, True, True), (2, False, True)]      # elo = 2, ehi = 1; the short-strip rule: slice 1 is within two slices of both ends
+    assert halo_visits(1, 1, True, True) == [(0, True, True)] and halo_visits(2, 3, False, True) == [(0, False, True), (1, False, True)]
+    codes = np.full((2 * SLICE, 2), PAD, dtype=np.uint8)
+    codes[SLICE:SLICE + 4] = [[3, 255], [3, 4], [254, 7], [9, 8]]          # lane 0: one diagonal | 255 beside an entry; lane 1: 254 beside an entry | two diagonals
+    assert gather_kinds(codes, [1]) == (1, 2, 1) and gather_kinds(codes, [0]) == (0, 0, 0)
+    halo_checked = 0
+    for strip, w, use_dict in halo_cases():
+        seen = np.zeros(3, dtype=np.int64)
+        fams = halo_families(strip, w)
+        assert "bands" in fams and ("crossed" in fams or strip.reach == 1) and ("holes" in fams) == (2 * strip.rows >= strip.n), (strip.name, w, fams)
+        for fam in fams:
+            mat = strip_matrix(oracle, strip, fam, w)
+            inner = halo_geometry(strip, mat)
+            assert len(inner) == max(0, strip.ns - strip.edge * (strip.lower + strip.upper)), (mat.name, inner)
+            assert mat.n == strip.n and oracle.hell_width(mat.ptr) == w == mat.lens.max(), (mat.name, oracle.hell_width(mat.ptr))
+            assert np.all(mat.lens[:strip.lo] == 0) and np.all(mat.lens[strip.lo + strip.rows:] == 0) and mat.col.max() < strip.n
+            if fam == "bands" and w > 1:                                                      # how far into the ghost ranges the entries reach
+                assert mat.col.min() == max(0, strip.lo - strip.reach) and mat.col.max() == min(strip.n - 1, strip.lo + strip.rows - 1 + strip.reach), mat.name
+                assert strip.reach < strip.halo or (mat.col.min() == 0 and mat.col.max() == strip.n - 1), mat.name      # ... to their first and last elements
+            for kind in ("sell8", "sell8v"):
+                ptr, col, val = mat.csr(np.float64, halo_schemes(kind, use_dict))
+                deltas, values, max_col = tables(ptr, col, val, w)
+                assert np.abs(deltas).max() == strip.reach and len(deltas) <= 254 and (kind == "sell8" or len(values) <= 255), (mat.name, kind)
+                if use_dict:
+                    buf = encode_sell8v(ptr, col, val, w, deltas, max_col, np.float64, values, mat.slots(w)) if kind == "sell8v" else \
+                        encode_sell8(ptr, col, val, w, deltas, max_col, np.float64, mat.slots(w)).reshape(strip.n // SLICE, -1)[:, :(w + 1) // 2 * 1024]
+                    reps = first_appearance(buf.reshape(strip.n // SLICE, -1))[1]
+                    assert strip.n // SLICE >= 64 and 2 <= len(reps) and 4 * len(reps) <= strip.n // SLICE, (mat.name, kind, len(reps))
+            k = np.array(gather_kinds(_coded(ptr, col, w, deltas, max_col, mat.slots(w))[2], inner))
+            assert not inner or k[HALO_FAMILIES.index(fam)] > 0, (mat.name, k.tolist())
+            seen += k
+            halo_checked += 1
+        assert strip.ns < 2 * strip.edge or strip.reach == 1 or np.all(seen > 0), (strip.name, w, seen.tolist())
+    assert halo_checked == 16 * 3 + 2 + 3 + 3 * 2 + 4 * 3
+    seams = strip_matrix(oracle, STRIPS["seams"], "bands", 3)                 # the +-1 diagonals cross both seams inside one lane
+    lo, end = STRIPS["seams"].lo, STRIPS["seams"].lo + STRIPS["seams"].rows
+    assert seams.col[seams.ptr[lo]] == lo - 1 and seams.col[seams.ptr[end - 1] - 1] == end - 1 and seams.col[seams.ptr[end] - 1] == end
 
     # the plan restatement
     assert (march_span_bytes(0, 0, 8), march_span_bytes(-600, 600, 8), march_span_bytes(-1, 1, 4), march_lds_bytes(-600, 600, 8)) == (0, 12288, 2048, 44032)

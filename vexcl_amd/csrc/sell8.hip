@@ -821,6 +821,26 @@ void sell8v_runs_kernel(long long n, long long nslices, V alpha, int append, int
 // stored order: bit-identical to CSR.
 // ---------------------------------------------------------------------------
 
+// What the pair product and its halo role (below) share beyond slices.hpp (this file is their only user).  pair_slice: a slice of ELL
+// width W as they read it -- WP code words per lane and kind of code; the code block (diagonal codes, then as many value codes) is
+// what a slice dictionary pools; stored values follow the diagonal codes.
+template <typename V, int W, bool VCODED>
+struct pair_slice {
+    static constexpr int WP = (W + 1) / 2;
+    static constexpr long long DIAG_BYTES = (long long)WP * 1024;
+    static constexpr long long CODE_BYTES = VCODED ? 2 * DIAG_BYTES : DIAG_BYTES;
+    static constexpr long long BYTES = VCODED ? CODE_BYTES : DIAG_BYTES + (long long)W * SLICE_ROWS * (long long)sizeof(V);
+};
+// gather_pair's d of ELL column j: the diagonal of the row that holds an entry (both padding: any table entry)
+template <int N>
+__device__ __forceinline__ int pair_delta(const unsigned (&c)[N], int j, const int *s_delta)
+{ const unsigned c0 = code_of(c, j, 0), c1 = code_of(c, j, 1); return s_delta[c0 < PAD_UNSAFE ? c0 : c1]; }
+// The value of a value-coded entry (ELL column j, row q of the lane): table entry 255 is 0.0, the padding.  The loop around it stays in
+// the kernels: with the stored values, xv or sum handed to a helper the pair kernels compile to other machine code.
+template <typename V, int NC, int NVC>
+__device__ __forceinline__ V coded_value(const unsigned (&c)[NC], const unsigned (&vc)[NVC], const V *s_value, int j, int q)
+{ return s_value[code_of(c, j, q) < PAD_UNSAFE ? code_of(vc, j, q) : 255u]; }
+
 template <typename V, int W, bool VCODED, bool DICT>
 __global__ __launch_bounds__(256)
 void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
@@ -828,8 +848,8 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
         const int *__restrict__ csr_ptr, const int *__restrict__ csr_col, const V *__restrict__ csr_val,
         const V *__restrict__ x, V *__restrict__ y, trav_dev trav, const char *__restrict__ pool, const int *__restrict__ blocks)
 {
-    constexpr int WP = (W + 1) / 2;
-    constexpr long long SLICE = VCODED ? (long long)WP * 2048 : ((long long)WP * 1024 + (long long)W * SLICE_ROWS * (long long)sizeof(V));
+    typedef pair_slice<V, W, VCODED> S;
+    constexpr int WP = S::WP;
     typedef typename vec2<V>::type V2;
     __shared__ int s_delta[256];
     __shared__ V s_value[VCODED ? 256 : 1];
@@ -849,8 +869,7 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
     // DICT (slice dictionary, below): the CODES of slice s are block blocks[s] of a small pool of distinct code blocks; the
     // pool lives in L1 / L2, so its loads are plain (cached) ones -- streamed codes keep their non-temporal loads.  Stored
     // values (VCODED = false) stay in the slice.
-    constexpr long long CODE_BYTES = VCODED ? (long long)WP * 2048 : (long long)WP * 1024;
-    const unsigned *cw = reinterpret_cast<const unsigned *>(DICT ? pool + (long long)blocks[sl] * CODE_BYTES : buf + sl * SLICE) + t;
+    const unsigned *cw = reinterpret_cast<const unsigned *>(DICT ? pool + (long long)blocks[sl] * S::CODE_BYTES : buf + sl * S::BYTES) + t;
     unsigned c[WP], vc[VCODED ? WP : 1];
 #pragma unroll
     for (int jp = 0; jp < WP; ++jp) {
@@ -859,7 +878,7 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
     }
     V2 v[VCODED ? 1 : W];
     if constexpr (!VCODED) {
-        const V *vp = reinterpret_cast<const V *>(buf + sl * SLICE + (long long)WP * 1024) + 2 * t;
+        const V *vp = reinterpret_cast<const V *>(buf + sl * S::BYTES + S::DIAG_BYTES) + 2 * t;
 #pragma unroll
         for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
     }
@@ -870,10 +889,7 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
     // table look-ups for every column first, then every gather
     int d[W];
 #pragma unroll
-    for (int j = 0; j < W; ++j) {
-        const unsigned c0 = code_of(c, j, 0), c1 = code_of(c, j, 1);
-        d[j] = s_delta[c0 < PAD_UNSAFE ? c0 : c1];
-    }
+    for (int j = 0; j < W; ++j) d[j] = pair_delta(c, j, s_delta);
     // the 16-byte load is skipped only when NO lane of the wave has a pair in a column (matrices without band structure);
     // lanes without one read the diagonal table instead
     V xv[W][2];
@@ -885,8 +901,8 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             V a;
-            if constexpr (VCODED) a = s_value[code_of(c, j, q) < PAD_UNSAFE ? code_of(vc, j, q) : 255u];   // entry 255 is 0.0
-            else a = v[j][q];                                                                          // stored as 0 for padding
+            if constexpr (VCODED) a = coded_value(c, vc, s_value, j, q);
+            else a = v[j][q];                                                              // stored as 0 for padding
             sum[q] += a * xv[j][q];
         }
     add_csr_tail<V>(n, i, csr_ptr, csr_col, csr_val, &x, &sum);
@@ -900,16 +916,16 @@ void sell8_pair_kernel(long long n, long long nslices, V alpha, int append,
 // stored form.  Slices whose diagonals stay inside the device's own rows run the pair product as it is (x and y moved by the ghost
 // range); the slices within `reach` of an end -- dispatched LAST -- wait for the neighbour's "x is final" flag and take every element
 // of x through a translation ghost-below / own / ghost-above (two 8-byte requests per column instead of one 16-byte pair: a pair may
-// straddle the seam).  Same codes, same order of the sums: the BITS of the one-device product.
+// straddle the seam).  Same codes, same order of the sums: the BITS of the one-device product.  Written here: the role alone (dispatch
+// order, flags, the move by the ghost range, the translated access, the store bound).  One process, every form: tests/test_gpu_sell8_kernels.py, test_halo_*.
 template <typename V, int W, bool VCODED, bool DICT>
 __global__ __launch_bounds__(256)
 void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
         const char *__restrict__ buf, const int *__restrict__ deltas, const V *__restrict__ values,
         const V *__restrict__ x, V *__restrict__ y, const char *__restrict__ pool, const int *__restrict__ blocks, halo_dev H)
 {
-    constexpr int WP = (W + 1) / 2;
-    constexpr long long SLICE = VCODED ? (long long)WP * 2048 : ((long long)WP * 1024 + (long long)W * SLICE_ROWS * (long long)sizeof(V));
-    constexpr long long CODE_BYTES = VCODED ? (long long)WP * 2048 : (long long)WP * 1024;
+    typedef pair_slice<V, W, VCODED> S;
+    constexpr int WP = S::WP;
     typedef typename vec2<V>::type V2;
     __shared__ int s_delta[256];
     __shared__ V s_value[VCODED ? 256 : 1];
@@ -938,7 +954,7 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     halo_announce(H, step);
     const long long sl = so + hlo / SLICE_ROWS;                              // slice of the stored strip
     const long long i = sl * SLICE_ROWS + 2 * t;                             // row, stored numbering
-    const unsigned *cw = reinterpret_cast<const unsigned *>(DICT ? pool + (long long)blocks[sl] * CODE_BYTES : buf + sl * SLICE) + t;
+    const unsigned *cw = reinterpret_cast<const unsigned *>(DICT ? pool + (long long)blocks[sl] * S::CODE_BYTES : buf + sl * S::BYTES) + t;
     unsigned c[WP], vc[VCODED ? WP : 1];
 #pragma unroll
     for (int jp = 0; jp < WP; ++jp) {
@@ -947,7 +963,7 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     }
     V2 v[VCODED ? 1 : W];
     if constexpr (!VCODED) {
-        const V *vp = reinterpret_cast<const V *>(buf + sl * SLICE + (long long)WP * 1024) + 2 * t;
+        const V *vp = reinterpret_cast<const V *>(buf + sl * S::BYTES + S::DIAG_BYTES) + 2 * t;
 #pragma unroll
         for (int j = 0; j < W; ++j) v[j] = __builtin_nontemporal_load(reinterpret_cast<const V2 *>(vp + j * SLICE_ROWS));
     }
@@ -958,32 +974,12 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     if (edge_wg) ghosts_ok = halo_wait(H, step, need_lo && H.lo, need_hi && H.hi, &s_flag);
     const V *xe = x - hlo;                                                // x in stored numbering (own range only)
     V xv[W][2];
-    if (!edge_wg) {             // a copy of gather_pair (slices.hpp) on xe: to move onto it once this kernel has a one-process test
+    if (!edge_wg) {                                                       // the pair product as it is, on xe
         int d[W];
 #pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            d[j] = s_delta[c0 < PAD_UNSAFE ? c0 : c1];
-        }
+        for (int j = 0; j < W; ++j) d[j] = pair_delta(c, j, s_delta);
 #pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
-            const bool m0 = c0 < PAD_UNSAFE, m1 = c1 < PAD_UNSAFE;
-            const bool pair = (c0 == c1) || (c0 == PAD && m1) || (c1 == PAD && m0);
-            const bool use16 = pair && (m0 || m1);
-            V2 p = {V(0), V(0)};
-            if (__builtin_amdgcn_ballot_w64(use16) != 0) {
-                const V *px = use16 ? xe + (i + d[j]) : reinterpret_cast<const V *>(deltas);
-                __builtin_memcpy(&p, px, sizeof(V2));
-            }
-            xv[j][0] = p.x; xv[j][1] = p.y;
-            if (!pair) {
-                if (m0) xv[j][0] = xe[i + s_delta[c0]];
-                if (m1) xv[j][1] = xe[i + 1 + s_delta[c1]];
-            }
-            xv[j][0] = m0 ? xv[j][0] : V(0);
-            xv[j][1] = m1 ? xv[j][1] : V(0);
-        }
+        for (int j = 0; j < W; ++j) gather_pair<V>(xe, i, code_of(c, j, 0), code_of(c, j, 1), d[j], s_delta, deltas, xv[j][0], xv[j][1]);
     } else {
         const long long own_end = hlo + own_rows;
         const V *glo = reinterpret_cast<const V *>(H.lo), *ghi = reinterpret_cast<const V *>(H.hi);
@@ -994,7 +990,7 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
         };
 #pragma unroll
         for (int j = 0; j < W; ++j) {
-            const unsigned c0 = (c[j >> 1] >> (16 * (j & 1))) & 255u, c1 = (c[j >> 1] >> (16 * (j & 1) + 8)) & 255u;
+            const unsigned c0 = code_of(c, j, 0), c1 = code_of(c, j, 1);
             xv[j][0] = c0 < PAD_UNSAFE ? at(i + s_delta[c0]) : V(0);
             xv[j][1] = c1 < PAD_UNSAFE ? at(i + 1 + s_delta[c1]) : V(0);
         }
@@ -1004,10 +1000,9 @@ void sell8_pair_halo_kernel(long long own_rows, V alpha, int append,
     for (int j = 0; j < W; ++j)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            const int sh = 16 * (j & 1) + 8 * q;
             V a;
-            if constexpr (VCODED) a = s_value[((c[j >> 1] >> sh) & 255u) < PAD_UNSAFE ? (vc[j >> 1] >> sh) & 255u : 255u];
-            else a = v[j][q];
+            if constexpr (VCODED) a = coded_value(c, vc, s_value, j, q);
+            else a = v[j][q];                                                              // stored as 0 for padding
             sum[q] += a * xv[j][q];
         }
     store_pair<V>(hlo + own_rows, i, alpha, append, sum, y - hlo);
