@@ -87,6 +87,7 @@ enum env_id {
     ENV_VEXHIP_PLANE_FORCE,
     ENV_VEXHIP_PLANE_STORE,
     ENV_VEXHIP_PLANE_TILE,
+    ENV_VEXHIP_PLANE_WALK,
     ENV_VEXHIP_RCCL_SELF,
     ENV_VEXHIP_SELL_XLOAD,
     ENV_VEXHIP_SETUP_TRACE,

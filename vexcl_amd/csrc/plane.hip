@@ -389,6 +389,232 @@ void sell8_plane_kernel(const double *__restrict__ x, double *__restrict__ y, do
     }
 }
 
+// The walk of the headline shape -- tiles of two lines, no ghost planes, not flat -- with no stretch in which a workgroup has no request
+// in flight (one walk per CU is all that is resident there: a walk that waits leaves the CU's share of HBM idle).  The steps, the sums
+// and their order are those of plane_walk; what differs is WHEN things are asked for:
+//   * the walk's first x requests and the classes of its first four planes go out first, the tables are read behind them;
+//   * where the first plane uses a class other than the hot one, that class is decoded before the first look, so plane 0 of a grid --
+//     all boundary lines -- takes fast steps;
+//   * the classes of the tile's lines come through SCALAR loads, requested at the top of a group of four steps for the four planes
+//     behind it (cw[]) and looked at when the group is done.  Scalar loads are counted apart from the vector requests, so no look waits
+//     for an x request or a store (plane_walk's look-up every 64 planes is two dependent vector loads behind a full drain), and they
+//     cost no vector register: the kernel sits at its 128, and a class kept in a vector register for the 64 steps of a window was
+//     spilled and came back through the vector memory pipeline, behind every request of the walk.  Every class word is read once per
+//     walk; a slow step takes its classes from the same registers, and a change of the other class needs nothing re-read.
+// The last three planes of a grid still take slow steps (their requests would leave x): the rule `zh` of plane_walk.
+// VEXHIP_PLANE_WALK=0 keeps plane_walk for this shape (tools/plane_walk_ab.py times the two in one process).
+template <int ZM, int STORE_AUX>
+__device__ __forceinline__
+void plane_walk_ahead(const double *__restrict__ x, double *__restrict__ y, double alpha, const double *__restrict__ zs, double beta,
+        const int *__restrict__ blocks, const char *__restrict__ pool, const int *__restrict__ deltas, const double *__restrict__ values,
+        const plane_dev &pd)
+{
+    constexpr int TY = 2;
+    __shared__ int s_slot[256];
+    __shared__ double s_value[256];
+    __shared__ double s_other[15][256];
+
+    const int t = threadIdx.x;
+    const unsigned b = blockIdx.x;
+    const unsigned xcd = b & 7u, q = b >> 3;
+    const int zc = (int)(q / (unsigned)pd.tpx), tyl = (int)(q - (unsigned)zc * (unsigned)pd.tpx);
+    const int tile = (int)xcd * pd.tpx + tyl;
+    if (tile >= pd.tiles) return;                                   // the whole workgroup
+    const int y0 = TY * tile;
+    int z = zc * pd.depth;
+    const int zend = z + pd.depth < pd.nz ? z + pd.depth : pd.nz;
+    if (z >= zend) return;
+    const int ny = pd.ny;
+    const int nslices = (int)pd.nslices, xlines = (int)pd.xlines;
+    const long long x_last = pd.x_last;
+    const unsigned lane_b = 16u * (unsigned)t;
+    const int edge_b = (t >> 6) * 1024 + ((t & 63) == 63 ? 1024 : -8);
+
+    // the clamped requests of plane_walk (prologue, slow steps)
+    auto line_of = [&](int zz, int l) -> int {
+        int li = zz * ny + (y0 - 1 + l);
+        li = li < 0 ? 0 : li; li = li >= xlines ? xlines - 1 : li;
+        return li;
+    };
+    auto ld = [&](int zz, int l) -> d2 {
+        return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(x + (long long)line_of(zz, l) * PL_ROWS) + lane_b);
+    };
+    auto edge = [&](int zz, int l) -> double {
+        long long i = (long long)line_of(zz, l) * PL_ROWS + (edge_b >> 3);
+        i = i < 0 ? 0 : i; i = i > x_last ? x_last : i;
+        return x[i];
+    };
+    auto yold = [&](int zz, int l) -> d2 {
+        int li = zz * ny + (y0 + l);
+        li = li < 0 ? 0 : li; li = li >= nslices ? nslices - 1 : li;
+        return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(zs + (long long)li * PL_ROWS) + lane_b);
+    };
+
+    d2 Cs[4][TY], Hs[2][2], Yo[TY];
+    double Es[2][TY];
+    const unsigned plane_b32 = (unsigned)ny * (unsigned)PL_LINE_B;
+    const int z_first = z;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double *>(x + ((long long)z_first * ny + (y0 - 1)) * PL_ROWS), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(ZM == 1 ? zs : x) + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
+    // fast steps need nothing clamped: planes up to z + 3 inside x, both lines inside y (the rule of plane_walk)
+    int zh = zend;
+    {
+        const int a = (xlines - 1 - TY - y0) / ny - 3, bb = (nslices - TY - y0) / ny - (ZM == 1 ? 1 : 0);
+        if (xlines - 1 - TY - y0 < 0 || nslices - TY - y0 < 0) zh = 0;
+        else { zh = zh < a + 1 ? zh : a + 1; zh = zh < bb + 1 ? zh : bb + 1; }
+    }
+
+    // ---- what depends on the geometry alone goes out first: the registers of plane z, the classes of the first four planes ----
+    fill_registers<ZM>(Cs, Hs, Es, Yo, z, true, ld, edge, yold);
+    // cw[i][l]: the class of tile line l in plane z + i (uniform: scalar loads; past the last line: the last line's, never looked at)
+    int cw[4][TY];
+    auto class_of = [&](int zz, int l) -> int {
+        const int li = zz * ny + (y0 + l);
+        return __builtin_amdgcn_readfirstlane(blocks[li < nslices ? li : nslices - 1]);
+    };
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int l = 0; l < TY; ++l) cw[i][l] = class_of(z + i, l);
+
+    // ---- the tables, behind the requests ----
+    s_slot[t] = 2 * position_of(deltas[t], pd.far); s_value[t] = values[t];
+    __syncthreads();
+    const int wp = (pd.w + 1) >> 1;
+    auto decode = [&](int blk) -> unsigned {                     // (plane_walk's)
+        if (pd.pitch > 0) return decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 2 * t, pd.pitch, s_value, s_other, t);
+        const unsigned *cw = reinterpret_cast<const unsigned *>(pool + (long long)blk * ((long long)wp * 2048)) + t;
+        unsigned dcw[4], vcw[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { dcw[u] = u < wp ? cw[u * 256] : 0xffffffffu; vcw[u] = u < wp ? cw[(wp + u) * 256] : 0u; }
+#pragma unroll
+        for (int p = 0; p < 14; ++p) s_other[p][t] = 0.0;
+        unsigned bits = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const unsigned cword = dcw[j >> 1] >> (16 * (j & 1)), vword = vcw[j >> 1] >> (16 * (j & 1));
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const unsigned code = j < pd.w ? (cword >> (8 * r)) & 255u : 255u;
+                const bool real = code < PL_PAD_FIRST;
+                const int slot = real ? s_slot[code] + r : 14;
+                s_other[slot][t] = s_value[real ? (vword >> (8 * r)) & 255u : 255u];
+                bits |= (real ? 1u : 0u) << slot;
+            }
+        }
+        return bits & 0x3fffu;
+    };
+    const int hot = pd.hot;
+    double aH[7][2];
+    unsigned long long mH[7][2];
+    take_hot(decode(hot), s_other, t, aH, mH);
+    unsigned bitsO = 0;
+    int other = -1;
+    // the first plane's first class that is not the hot one becomes the other class now
+#pragma unroll
+    for (int l = TY - 1; l >= 0; --l)
+        if (cw[0][l] != hot && z * ny + (y0 + l) < nslices) other = cw[0][l];
+    if (other >= 0) bitsO = decode(other);
+
+    // the look: can the planes z .. z + 3 take a group of four fast steps -- all below zh, every line of the hot or the other class?
+    unsigned use_hot = 0;                               // bit 4 l + i: line l of plane z + i uses the hot class
+    auto look = [&]() -> bool {
+        bool fast = z + 4 <= zh;
+        use_hot = 0;
+#pragma unroll
+        for (int l = 0; l < TY; ++l)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                fast = fast && (cw[i][l] == hot || cw[i][l] == other);
+                use_hot |= (cw[i][l] == hot ? 1u : 0u) << (4 * l + i);
+            }
+        return fast;
+    };
+    while (z < zend) {
+        if (look()) {
+            // A run of groups is entered with nothing outstanding (the prologue and a slow step have consumed what they requested last):
+            // said here, so that the waits inside the loop count the loop's own requests and not, for every group, the fewer ones that
+            // follow a request of a slow step.
+            __builtin_amdgcn_s_waitcnt(0x0f70);             // vmcnt(0)
+            do {
+                // the classes of the four planes behind the group: requested now, looked at when the group is done
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int l = 0; l < TY; ++l) cw[i][l] = class_of(z + 4 + i, l);
+                unsigned xo = (unsigned)((z + 2 - z_first) * plane_b32), yo = (unsigned)((z - z_first) * plane_b32);
+                auto fast_step = [&](d2 (&P)[TY], d2 (&C)[TY], d2 (&N)[TY], d2 (&Hl)[2], double (&E)[TY]) {
+                    d2 o[TY];
+#pragma unroll
+                    for (int l = 0; l < TY; ++l) {
+                        double xs[2][7], sm[2] = {};
+                        stencil_x(P, C, N, Hl, E, l, xs);
+                        if (use_hot & (1u << (4 * l))) hot_sums(sm, aH, mH, xs); else other_sums(sm, s_other, t, bitsO, xs);      // uniform
+                        o[l] = add_addend<ZM>(alpha, sm, beta, Yo[l], C[l]);
+                    }
+                    use_hot >>= 1;
+#pragma unroll
+                    for (int l = 0; l < TY; ++l) store16<STORE_AUX>(o[l], ry, (int)lane_b, yo + l * PL_LINE_B);
+                    if (ZM == 1) {
+#pragma unroll
+                        for (int l = 0; l < TY; ++l) Yo[l] = load16<double>(rz, (int)lane_b, yo + plane_b32 + l * PL_LINE_B);
+                    }
+                    Hl[0] = load16<double>(rx, (int)lane_b, xo);
+                    Hl[1] = load16<double>(rx, (int)lane_b, xo + (TY + 1) * PL_LINE_B);
+#pragma unroll
+                    for (int l = 0; l < TY; ++l) {
+                        P[l] = load16<double>(rx, (int)lane_b, xo + plane_b32 + (l + 1) * PL_LINE_B);
+                        E[l] = load_edge<double>(rx, edge_b + 8, xo + (l + 1) * PL_LINE_B - 8u);
+                    }
+                    xo += plane_b32; yo += plane_b32; ++z;
+                };
+                fast_group(fast_step, Cs, Hs, Es);
+            } while (look());
+            if (z >= zend) break;
+        }
+        // ---- a slow step (plane_walk's): a line needs another class decoded, the last planes (clamped requests), the ragged last plane,
+        // what a run leaves over after its groups of four ----
+#pragma unroll
+        for (int l = 0; l < TY; ++l) {
+            const int li = z * ny + (y0 + l);
+            if (li < nslices) {                                           // uniform
+                double xs[2][7], sm[2] = {};
+                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
+                const int blk = cw[0][l];
+                if (blk == hot) hot_sums(sm, aH, mH, xs);
+                else {
+                    if (blk != other) { bitsO = decode(blk); other = blk; }
+                    other_sums(sm, s_other, t, bitsO, xs);
+                }
+                const d2 o = add_addend<ZM>(alpha, sm, beta, Yo[l], Cs[1][l]);
+                __builtin_nontemporal_store(o, reinterpret_cast<d2 *>(reinterpret_cast<char *>(y + (long long)li * PL_ROWS) + lane_b));
+            }
+        }
+        rotate_by_copy<ZM>(Cs, Hs, Es, Yo, z, true, ld, edge, yold);
+        ++z;
+#pragma unroll
+        for (int l = 0; l < TY; ++l) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) cw[i][l] = cw[i + 1][l];
+            cw[3][l] = class_of(z + 3, l);
+        }
+    }
+}
+
+// (a namespace of its own, the kernel's name kept: profiles and the counter passes of bench.py find the headline kernel by that name)
+namespace ahead {
+template <int ZM, int STORE_AUX>
+__global__ __launch_bounds__(256, 4)
+void sell8_plane_kernel(const double *__restrict__ x, double *__restrict__ y, double alpha, const double *__restrict__ zs, double beta,
+        const int *__restrict__ blocks, const char *__restrict__ pool, const int *__restrict__ deltas, const double *__restrict__ values,
+        plane_dev pd)
+{
+    plane_walk_ahead<ZM, STORE_AUX>(x, y, alpha, zs, beta, blocks, pool, deltas, values, pd);
+}
+} // namespace ahead
+
 // The yardstick of the plane / march products (bench.py roofline.device_copy_hand): x copied to y with one 16-byte pair per lane,
 // no loop, non-temporal stores -- the same HBM traffic as the product (x once, y once) and nothing else to do.  6.23 TB/s at
 // 512^3 elements on the box where the library's copy (torch) reaches 4.94 (profiles/r04_pm_proto.json).
@@ -429,7 +655,13 @@ int plane_apply_axpby(int dev, void *stream, int64_t n, double alpha, int zm, co
     unsigned grid;
     if (int rc = plane_workgroups(pd, pd.nz, 0, 0, &grid)) return rc;
     const char *cpool = static_cast<const char *>(pool);
+    const char *walk = env(ENV_VEXHIP_PLANE_WALK);                           // 0: plane_walk for every shape; 1 / unset: plane_walk_ahead where it exists
+    const bool ahead = plane->tile == 2 && !plane->flat && !(walk && std::atoi(walk) == 0);
     with_launch_forms(zm, plane->store_policy, [&](auto ZM, auto AUX) {      // (the plan's policy: plane_geometry_with; the flat walk exists for tiles of two only)
+        if (ahead) {
+            ahead::sell8_plane_kernel<ZM(), AUX()><<<grid, 256, 0, as_stream(stream)>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd);
+            return;
+        }
         auto kernel = plane->tile == 4 ? sell8_plane_kernel<4, ZM(), AUX()> : plane->flat ? sell8_plane_kernel<2, ZM(), AUX(), false, true> : sell8_plane_kernel<2, ZM(), AUX()>;
         kernel<<<grid, 256, 0, as_stream(stream)>>>(x, y, alpha, zs, beta, blocks, cpool, deltas, values, pd, halo_dev());
     });

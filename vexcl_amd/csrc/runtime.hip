@@ -215,6 +215,7 @@ const char *const kEnvNames[ENV_COUNT] = {
     "VEXHIP_PLANE_FORCE",
     "VEXHIP_PLANE_STORE",
     "VEXHIP_PLANE_TILE",
+    "VEXHIP_PLANE_WALK",
     "VEXHIP_RCCL_SELF",
     "VEXHIP_SELL_XLOAD",
     "VEXHIP_SETUP_TRACE",
