@@ -190,6 +190,18 @@ def test_both_walks_on_hand_built_plans(G, oracle, case):
     both_walks(G, oracle, Run(G, oracle, case))
 
 
+# the matrix as SELL-512 code blocks (csrc/plane.hpp decode_block: an ELL width below 8, an odd number of column pairs, padding codes):
+# the block-form cases of test_gpu_plane_grid_kernels.py that have tiles of two lines -- 4 lines x 24 planes, walks of 8 planes
+BLOCK_CASES = [c for c in K.PLANE_CASES if c[0].startswith("blocks-w") and c[9]["tile"] == 2]
+
+
+@gpu
+@pytest.mark.parametrize("case", BLOCK_CASES, ids=[c[0] for c in BLOCK_CASES])
+def test_both_walks_on_code_blocks(G, oracle, case):
+    assert case[8] > 0 and [c[0] for c in BLOCK_CASES] == ["blocks-w2", "blocks-w4", "blocks-w6", "blocks-w8"]
+    both_walks(G, oracle, Run(G, oracle, case))
+
+
 @gpu
 def test_unset_selects_the_new_walk_and_other_shapes_ignore_the_switch(G, oracle):
     """Unset is 1 (the same bytes, whatever they are, is all a product can show); tiles of four and flat plans have one walk."""

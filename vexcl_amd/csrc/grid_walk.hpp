@@ -85,6 +85,7 @@ void grid_walk(const V *__restrict__ x, V *__restrict__ y, V alpha, const V *__r
     take_hot(decode(hot), s_other, t, aH, mH);
     unsigned bitsO = 0;
     int other = -1;                             // what s_other holds now is the hot class's: never asked for
+    const line_terms<V, 7 * R, MAXT> terms = {aH, mH, s_other, hot, other, bitsO, t, alpha, beta};
 
     // clamped requests (prologue, slow steps): line `l` of the tile's window (0 = the line above the tile, 1 .. TY = the tile,
     // TY + 1 = the line below) in plane zz, element by element.  What lies outside x is never referenced by an entry; what is
@@ -200,15 +201,7 @@ void grid_walk(const V *__restrict__ x, V *__restrict__ y, V alpha, const V *__r
         for (int l = 0; l < TY; ++l) {
             const long long li = (long long)z * ny + (y0 + l);
             if (l < nl && li < lines) {                                   // uniform
-                V xs[R][7], s[R] = {};
-                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
-                const int cls = __builtin_amdgcn_readfirstlane(line_class[li]);
-                if (cls == hot) hot_sums(s, aH, mH, xs);
-                else {
-                    if (cls != other) { bitsO = decode(cls); other = cls; }
-                    other_sums(s, s_other, t, bitsO, xs);
-                }
-                const VEC o = add_addend<ZM>(alpha, s, beta, Yo[l], Cs[1][l]);
+                const VEC o = line_result<ZM>(terms, __builtin_amdgcn_readfirstlane(line_class[li]), decode, Cs, Hs, Es, Yo, l);
                 V *yr = y + li * nx + row0 + R * t;
 #pragma unroll
                 for (int r = 0; r < R; ++r) if (r < nv) { const V e = o[r]; __builtin_nontemporal_store(e, yr + r); }

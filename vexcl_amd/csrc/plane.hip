@@ -121,12 +121,8 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         }
         b -= npush;
     }
-    const unsigned xcd = b & 7u, q = b >> 3;
-    const int zc = (int)(q / (unsigned)pd.tpx), tyl = (int)(q - (unsigned)zc * (unsigned)pd.tpx);
-    const int tile = (int)xcd * pd.tpx + tyl;
-    if (tile >= pd.tiles) return;                                   // the whole workgroup
-    const int y0 = TY * tile;
-    int z, zend;
+    int y0, zc, z, zend;
+    if (!plane_tile(pd, b, TY, y0, zc)) return;                     // the whole workgroup
     [[maybe_unused]] bool second = false;
     [[maybe_unused]] int z2 = 0, zend2 = 0;
     if constexpr (HALO) {
@@ -143,11 +139,8 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
             // more: tools/r05_halo_timeline.py) -- one plane of work behind the flag instead of the whole chunk
             z = H.z0 + 1; zend = mid0; second = true; z2 = H.z0; zend2 = H.z0 + 1;
         } else { z = H.z0; zend = mid0; }
-    } else {
-        z = zc * pd.depth;
-        zend = z + pd.depth < pd.nz ? z + pd.depth : pd.nz;
-    }
-    if (z >= zend) return;
+        if (z >= zend) return;
+    } else if (!plane_chunk(pd, zc, z, zend)) return;
     [[maybe_unused]] const int z_first0 = z, mid_end = zend;
     if constexpr (HALO) {
         // push_blocks == 0: NO dedicated push workgroups -- the first 2 x 256 product workgroups each copy 1024 elements of a
@@ -165,41 +158,17 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         }
     }
     const int ny = pd.ny;
-    const int nslices = (int)pd.nslices, xlines = (int)pd.xlines;
-    const long long x_last = pd.x_last;
     const unsigned lane_b = 16u * (unsigned)t;
-    // the element beyond either end of the wave's 128 rows of a line: lane 63 reads the one behind them, every other lane the
-    // one in front (lane 0 uses it; one cache line for the rest) -- byte offset from the start of the line
-    const int edge_b = (t >> 6) * 1024 + ((t & 63) == 63 ? 1024 : -8);
+    const int edge_b = edge_offset(t, 8);
 
     s_slot[t] = 2 * position_of(deltas[t], pd.far); s_value[t] = values[t];
     __syncthreads();
 
-    // ---- a dictionary block -> values (into s_other) and validity (returned) of this lane's rows at the seven positions ----
+    // a dictionary block, or a class of the matrix stored by grid line (grid.hip) -> values (into s_other) and validity (returned)
     const int wp = (pd.w + 1) >> 1;
     auto decode = [&](int blk) -> unsigned {
-        // the matrix stored by grid line (grid.hip): a value code per position and row, 255 = no entry
-        if (pd.pitch > 0) return decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 2 * t, pd.pitch, s_value, s_other, t);
-        const unsigned *cw = reinterpret_cast<const unsigned *>(pool + (long long)blk * ((long long)wp * 2048)) + t;
-        unsigned dcw[4], vcw[4];                // diagonal codes, value codes: one word per pair of ELL columns
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { dcw[u] = u < wp ? cw[u * 256] : 0xffffffffu; vcw[u] = u < wp ? cw[(wp + u) * 256] : 0u; }
-#pragma unroll
-        for (int p = 0; p < 14; ++p) s_other[p][t] = 0.0;
-        unsigned bits = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const unsigned cword = dcw[j >> 1] >> (16 * (j & 1)), vword = vcw[j >> 1] >> (16 * (j & 1));
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const unsigned code = j < pd.w ? (cword >> (8 * r)) & 255u : 255u;
-                const bool real = code < PL_PAD_FIRST;
-                const int slot = real ? s_slot[code] + r : 14;
-                s_other[slot][t] = s_value[real ? (vword >> (8 * r)) & 255u : 255u];      // entry 255 of the table is 0.0
-                bits |= (real ? 1u : 0u) << slot;
-            }
-        }
-        return bits & 0x3fffu;
+        return pd.pitch > 0 ? decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 2 * t, pd.pitch, s_value, s_other, t)
+                            : decode_block(pool, blk, pd.w, wp, s_slot, s_value, s_other, t);
     };
 
     const int hot = pd.hot;
@@ -208,19 +177,14 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
     take_hot(decode(hot), s_other, t, aH, mH);
     unsigned bitsO = 0;
     int other = -1;                             // what s_other holds now is the hot block's: never asked for
+    const line_terms<double, 15, 256> terms = {aH, mH, s_other, hot, other, bitsO, t, alpha, beta};
 
-    // clamped requests (prologue, slow steps): line `l` of the tile's window (0 = the line above the tile, 1 .. TY = the tile,
-    // TY + 1 = the line below) in plane zz.  A line outside x is never referenced by an entry; what is loaded in its place is
-    // multiplied by +0.0 behind a mask
-    // HALO: the lines of x and y that exist are those of the planes [z0, z1); the plane below / above them is the ghost plane
-    const int line_lo = HALO ? H.z0 * ny : 0, line_hi = HALO ? H.z1 * ny : xlines;       // x: [line_lo, line_hi)
-    const int yline_hi = HALO ? H.z1 * ny : nslices;
+    // clamped requests (plane.hpp).  HALO: the lines of x and y that exist are those of the planes [z0, z1); the plane below / above
+    // them is the ghost plane
+    const int line_lo = HALO ? H.z0 * ny : 0, line_hi = HALO ? H.z1 * ny : (int)pd.xlines;       // x: [line_lo, line_hi)
+    const int yline_hi = HALO ? H.z1 * ny : (int)pd.nslices;
+    const clamped_requests<double> own = {x, zs, ny, y0, line_lo, line_hi, yline_hi, HALO ? (long long)line_hi * PL_ROWS - 1 : pd.x_last, lane_b, edge_b};
     [[maybe_unused]] bool got_lo = false, got_hi = false, ghost_bad = false;
-    auto line_of = [&](int zz, int l) -> int {
-        int li = zz * ny + (y0 - 1 + l);
-        li = li < line_lo ? line_lo : li; li = li >= line_hi ? line_hi - 1 : li;
-        return li;
-    };
     auto ld = [&](int zz, int l) -> d2 {
         if constexpr (HALO) {
             const int li = zz * ny + (y0 - 1 + l);                                   // uniform
@@ -253,27 +217,16 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
                 return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(g + (long long)gl * PL_ROWS) + lane_b);
             }
         }
-        const char *p = reinterpret_cast<const char *>(x + (long long)line_of(zz, l) * PL_ROWS);
-        return *reinterpret_cast<const d2 *>(p + lane_b);
+        return own.ld(zz, l);
     };
     auto edge = [&](int zz, int l) -> double {
         if constexpr (HALO) {
             const int li = zz * ny + (y0 - 1 + l);
             if (li < line_lo || li >= line_hi) return 0.0;                           // the +-1 neighbours inside a ghost line: no row of this rank has them
-            long long i = (long long)li * PL_ROWS + (edge_b >> 3);
-            const long long a = (long long)line_lo * PL_ROWS, e = (long long)line_hi * PL_ROWS - 1;
-            i = i < a ? a : i; i = i > e ? e : i;
-            return x[i];
         }
-        long long i = (long long)line_of(zz, l) * PL_ROWS + (edge_b >> 3);
-        i = i < 0 ? 0 : i; i = i > x_last ? x_last : i;
-        return x[i];
+        return own.edge(zz, l);
     };
-    auto yold = [&](int zz, int l) -> d2 {
-        int li = zz * ny + (y0 + l);
-        li = li < line_lo ? line_lo : li; li = li >= yline_hi ? yline_hi - 1 : li;
-        return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(zs + (long long)li * PL_ROWS) + lane_b);
-    };
+    auto yold = [&](int zz, int l) -> d2 { return own.yold(zz, l); };
 
     // ---- the registers of the walk (walk.hpp), filled for plane z; which block a line uses is known for up to 64 planes ahead
     // (fast_run: one look at blocks[] per entry) ----
@@ -292,13 +245,7 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(ZM == 1 ? zs : x) + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
     fill_registers<ZM>(Cs, Hs, Es, Yo, z, !FLAT, ld, edge, yold);
 
-    // fast steps need nothing clamped: planes up to z + 3 inside x, both lines inside y
-    int zh = zend;
-    {
-        const int a = (line_hi - 1 - TY - y0) / ny - 3, bb = (yline_hi - TY - y0) / ny - (ZM == 1 ? 1 : 0);      // largest z with (z+3) ny + y0 + TY <= xlines - 1 / z ny + y0 + TY - 1 <= nslices - 1 ('+=': the old y is requested one plane ahead -- inside y also when x is longer than y)
-        if (line_hi - 1 - TY - y0 < 0 || yline_hi - TY - y0 < 0) zh = 0;
-        else { zh = zh < a + 1 ? zh : a + 1; zh = zh < bb + 1 ? zh : bb + 1; }
-    }
+    const int zh = fast_limit(zend, ny, y0, TY, line_hi, yline_hi, ZM == 1);
 
     while (z < zend) {
         unsigned long long use_hot[TY];
@@ -347,15 +294,7 @@ void plane_walk(const double *__restrict__ x, double *__restrict__ y, double alp
         for (int l = 0; l < TY; ++l) {
             const int li = z * ny + (y0 + l);
             if (li < yline_hi) {                                          // uniform
-                double xs[2][7], s[2] = {};
-                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
-                const int blk = __builtin_amdgcn_readfirstlane(blocks[li]);
-                if (blk == hot) hot_sums(s, aH, mH, xs);
-                else {
-                    if (blk != other) { bitsO = decode(blk); other = blk; }
-                    other_sums(s, s_other, t, bitsO, xs);
-                }
-                const d2 o = add_addend<ZM>(alpha, s, beta, Yo[l], Cs[1][l]);
+                const d2 o = line_result<ZM>(terms, __builtin_amdgcn_readfirstlane(blocks[li]), decode, Cs, Hs, Es, Yo, l);
                 __builtin_nontemporal_store(o, reinterpret_cast<d2 *>(reinterpret_cast<char *>(y + (long long)li * PL_ROWS) + lane_b));
             }
         }
@@ -415,40 +354,17 @@ void plane_walk_ahead(const double *__restrict__ x, double *__restrict__ y, doub
     __shared__ double s_other[15][256];
 
     const int t = threadIdx.x;
-    const unsigned b = blockIdx.x;
-    const unsigned xcd = b & 7u, q = b >> 3;
-    const int zc = (int)(q / (unsigned)pd.tpx), tyl = (int)(q - (unsigned)zc * (unsigned)pd.tpx);
-    const int tile = (int)xcd * pd.tpx + tyl;
-    if (tile >= pd.tiles) return;                                   // the whole workgroup
-    const int y0 = TY * tile;
-    int z = zc * pd.depth;
-    const int zend = z + pd.depth < pd.nz ? z + pd.depth : pd.nz;
-    if (z >= zend) return;
+    int y0, zc, z, zend;
+    if (!plane_tile(pd, blockIdx.x, TY, y0, zc)) return;           // the whole workgroup
+    if (!plane_chunk(pd, zc, z, zend)) return;
     const int ny = pd.ny;
     const int nslices = (int)pd.nslices, xlines = (int)pd.xlines;
-    const long long x_last = pd.x_last;
     const unsigned lane_b = 16u * (unsigned)t;
-    const int edge_b = (t >> 6) * 1024 + ((t & 63) == 63 ? 1024 : -8);
-
-    // the clamped requests of plane_walk (prologue, slow steps)
-    auto line_of = [&](int zz, int l) -> int {
-        int li = zz * ny + (y0 - 1 + l);
-        li = li < 0 ? 0 : li; li = li >= xlines ? xlines - 1 : li;
-        return li;
-    };
-    auto ld = [&](int zz, int l) -> d2 {
-        return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(x + (long long)line_of(zz, l) * PL_ROWS) + lane_b);
-    };
-    auto edge = [&](int zz, int l) -> double {
-        long long i = (long long)line_of(zz, l) * PL_ROWS + (edge_b >> 3);
-        i = i < 0 ? 0 : i; i = i > x_last ? x_last : i;
-        return x[i];
-    };
-    auto yold = [&](int zz, int l) -> d2 {
-        int li = zz * ny + (y0 + l);
-        li = li < 0 ? 0 : li; li = li >= nslices ? nslices - 1 : li;
-        return *reinterpret_cast<const d2 *>(reinterpret_cast<const char *>(zs + (long long)li * PL_ROWS) + lane_b);
-    };
+    const int edge_b = edge_offset(t, 8);
+    const clamped_requests<double> own = {x, zs, ny, y0, 0, xlines, nslices, pd.x_last, lane_b, edge_b};
+    auto ld = [&](int zz, int l) { return own.ld(zz, l); };
+    auto edge = [&](int zz, int l) { return own.edge(zz, l); };
+    auto yold = [&](int zz, int l) { return own.yold(zz, l); };
 
     d2 Cs[4][TY], Hs[2][2], Yo[TY];
     double Es[2][TY];
@@ -458,13 +374,7 @@ void plane_walk_ahead(const double *__restrict__ x, double *__restrict__ y, doub
         const_cast<double *>(x + ((long long)z_first * ny + (y0 - 1)) * PL_ROWS), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(ZM == 1 ? zs : x) + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
-    // fast steps need nothing clamped: planes up to z + 3 inside x, both lines inside y (the rule of plane_walk)
-    int zh = zend;
-    {
-        const int a = (xlines - 1 - TY - y0) / ny - 3, bb = (nslices - TY - y0) / ny - (ZM == 1 ? 1 : 0);
-        if (xlines - 1 - TY - y0 < 0 || nslices - TY - y0 < 0) zh = 0;
-        else { zh = zh < a + 1 ? zh : a + 1; zh = zh < bb + 1 ? zh : bb + 1; }
-    }
+    const int zh = fast_limit(zend, ny, y0, TY, xlines, nslices, ZM == 1);
 
     // ---- what depends on the geometry alone goes out first: the registers of plane z, the classes of the first four planes ----
     fill_registers<ZM>(Cs, Hs, Es, Yo, z, true, ld, edge, yold);
@@ -483,28 +393,9 @@ void plane_walk_ahead(const double *__restrict__ x, double *__restrict__ y, doub
     s_slot[t] = 2 * position_of(deltas[t], pd.far); s_value[t] = values[t];
     __syncthreads();
     const int wp = (pd.w + 1) >> 1;
-    auto decode = [&](int blk) -> unsigned {                     // (plane_walk's)
-        if (pd.pitch > 0) return decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 2 * t, pd.pitch, s_value, s_other, t);
-        const unsigned *cw = reinterpret_cast<const unsigned *>(pool + (long long)blk * ((long long)wp * 2048)) + t;
-        unsigned dcw[4], vcw[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { dcw[u] = u < wp ? cw[u * 256] : 0xffffffffu; vcw[u] = u < wp ? cw[(wp + u) * 256] : 0u; }
-#pragma unroll
-        for (int p = 0; p < 14; ++p) s_other[p][t] = 0.0;
-        unsigned bits = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const unsigned cword = dcw[j >> 1] >> (16 * (j & 1)), vword = vcw[j >> 1] >> (16 * (j & 1));
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const unsigned code = j < pd.w ? (cword >> (8 * r)) & 255u : 255u;
-                const bool real = code < PL_PAD_FIRST;
-                const int slot = real ? s_slot[code] + r : 14;
-                s_other[slot][t] = s_value[real ? (vword >> (8 * r)) & 255u : 255u];
-                bits |= (real ? 1u : 0u) << slot;
-            }
-        }
-        return bits & 0x3fffu;
+    auto decode = [&](int blk) -> unsigned {
+        return pd.pitch > 0 ? decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 2 * t, pd.pitch, s_value, s_other, t)
+                            : decode_block(pool, blk, pd.w, wp, s_slot, s_value, s_other, t);
     };
     const int hot = pd.hot;
     double aH[7][2];
@@ -512,6 +403,7 @@ void plane_walk_ahead(const double *__restrict__ x, double *__restrict__ y, doub
     take_hot(decode(hot), s_other, t, aH, mH);
     unsigned bitsO = 0;
     int other = -1;
+    const line_terms<double, 15, 256> terms = {aH, mH, s_other, hot, other, bitsO, t, alpha, beta};
     // the first plane's first class that is not the hot one becomes the other class now
 #pragma unroll
     for (int l = TY - 1; l >= 0; --l)
@@ -574,21 +466,12 @@ void plane_walk_ahead(const double *__restrict__ x, double *__restrict__ y, doub
             } while (look());
             if (z >= zend) break;
         }
-        // ---- a slow step (plane_walk's): a line needs another class decoded, the last planes (clamped requests), the ragged last plane,
-        // what a run leaves over after its groups of four ----
+        // ---- a slow step, as in plane_walk; the classes come from cw[0] ----
 #pragma unroll
         for (int l = 0; l < TY; ++l) {
             const int li = z * ny + (y0 + l);
             if (li < nslices) {                                           // uniform
-                double xs[2][7], sm[2] = {};
-                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
-                const int blk = cw[0][l];
-                if (blk == hot) hot_sums(sm, aH, mH, xs);
-                else {
-                    if (blk != other) { bitsO = decode(blk); other = blk; }
-                    other_sums(sm, s_other, t, bitsO, xs);
-                }
-                const d2 o = add_addend<ZM>(alpha, sm, beta, Yo[l], Cs[1][l]);
+                const d2 o = line_result<ZM>(terms, cw[0][l], decode, Cs, Hs, Es, Yo, l);
                 __builtin_nontemporal_store(o, reinterpret_cast<d2 *>(reinterpret_cast<char *>(y + (long long)li * PL_ROWS) + lane_b));
             }
         }

@@ -42,13 +42,8 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
     __shared__ float s_other[29][P32_LANES];
 
     const int t = threadIdx.x;
-    const unsigned b = blockIdx.x;
-    const unsigned xcd = b & 7u, q = b >> 3;
-    const int zc = (int)(q / (unsigned)pd.tpx), tyl = (int)(q - (unsigned)zc * (unsigned)pd.tpx);
-    const int tile = (int)xcd * pd.tpx + tyl;
-    if (tile >= pd.tiles) return;                                   // the whole workgroup
-    const int y0 = TY * tile;
-    int z, zend_;
+    int y0, zc, z, zend_;
+    if (!plane_tile(pd, blockIdx.x, TY, y0, zc)) return;           // the whole workgroup
     [[maybe_unused]] bool ghost_bad = false;
     [[maybe_unused]] __shared__ int s_flag;
     if constexpr (HALO) {
@@ -57,56 +52,23 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
         z = H.z0 + c * pd.depth; zend_ = z + pd.depth < H.z1 ? z + pd.depth : H.z1;
         if (zc >= nch || z >= zend_) return;
         ghost_bad = !halo_wait(H, step, H.lo && z == H.z0, H.hi && zend_ == H.z1, &s_flag);
-    } else {
-        z = zc * pd.depth;
-        zend_ = z + pd.depth < pd.nz ? z + pd.depth : pd.nz;
-        if (z >= zend_) return;
-    }
+    } else if (!plane_chunk(pd, zc, z, zend_)) return;
     const int zend = zend_;
     const int ny = pd.ny;
     // HALO: the lines of x and y that exist are those of the planes [z0, z1)
     const int line_lo = HALO ? H.z0 * ny : 0;
     const int nslices = HALO ? H.z1 * ny : (int)pd.nslices, xlines = HALO ? H.z1 * ny : (int)pd.xlines;
-    const long long x_last = HALO ? (long long)H.z1 * ny * PL_ROWS - 1 : pd.x_last;
     const unsigned lane_b = 16u * (unsigned)t;
-    // the element beyond either end of the wave's 256 rows of a line: lane 63 reads the one behind them, every other lane the
-    // one in front (lane 0 uses it) -- byte offset from the start of the line
-    const int edge_b = (t >> 6) * 1024 + ((t & 63) == 63 ? 1024 : -4);
+    const int edge_b = edge_offset(t, 4);
 
     for (int i = t; i < 256; i += P32_LANES) { s_slot[i] = 4 * position_of(deltas[i], pd.far); s_value[i] = values[i]; }
     __syncthreads();
 
-    // ---- a dictionary block -> values (into s_other) and validity (returned) of this lane's four rows at the seven positions ----
+    // a dictionary block, or a class of the matrix stored by grid line (grid.hip) -> values (into s_other) and validity (returned)
     const int wp = (pd.w + 1) >> 1;
     auto decode = [&](int blk) -> unsigned {
-        // the matrix stored by grid line (grid.hip): a value code per position and row, 255 = no entry
-        if (pd.pitch > 0) return decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 4 * t, pd.pitch, s_value, s_other, t);
-        // a code block: per pair of ELL columns 256 words of diagonal codes, then as many of value codes; word i holds rows 2i, 2i + 1
-        const unsigned *cw = reinterpret_cast<const unsigned *>(pool + (long long)blk * ((long long)wp * 2048)) + 2 * t;
-        unsigned dcw[4][2], vcw[4][2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { dcw[u][h] = u < wp ? cw[u * 256 + h] : 0xffffffffu; vcw[u][h] = u < wp ? cw[(wp + u) * 256 + h] : 0u; }
-#pragma unroll
-        for (int p = 0; p < 28; ++p) s_other[p][t] = 0.0f;
-        unsigned bits = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned cword = dcw[j >> 1][h] >> (16 * (j & 1)), vword = vcw[j >> 1][h] >> (16 * (j & 1));
-#pragma unroll
-                for (int r2 = 0; r2 < 2; ++r2) {
-                    const int r = 2 * h + r2;
-                    const unsigned code = j < pd.w ? (cword >> (8 * r2)) & 255u : 255u;
-                    const bool real = code < PL_PAD_FIRST;
-                    const int slot = real ? s_slot[code] + r : 28;
-                    s_other[slot][t] = s_value[real ? (vword >> (8 * r2)) & 255u : 255u];      // entry 255 of the table is 0.0
-                    bits |= (real ? 1u : 0u) << slot;
-                }
-            }
-        return bits & 0x0fffffffu;
+        return pd.pitch > 0 ? decode_table<false>(pool + (long long)blk * 7 * pd.pitch + 4 * t, pd.pitch, s_value, s_other, t)
+                            : decode_block(pool, blk, pd.w, wp, s_slot, s_value, s_other, t);
     };
 
     const int hot = pd.hot;
@@ -117,15 +79,10 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
     take_hot(decode(hot), s_other, t, aH, mH);
     unsigned bitsO = 0;
     int other = -1;                             // what s_other holds now is the hot block's: never asked for
+    const line_terms<float, 29, P32_LANES> terms = {aH, mH, s_other, hot, other, bitsO, t, alpha, beta};
 
-    // clamped requests (prologue, slow steps): line `l` of the tile's window (0 = the line above the tile, 1 .. TY = the tile,
-    // TY + 1 = the line below) in plane zz.  A line outside x is never referenced by an entry; what is loaded in its place is
-    // multiplied by +0.0 behind a mask
-    auto line_of = [&](int zz, int l) -> int {
-        int li = zz * ny + (y0 - 1 + l);
-        li = li < line_lo ? line_lo : li; li = li >= xlines ? xlines - 1 : li;
-        return li;
-    };
+    // clamped requests (plane.hpp); the ghost planes in front of them
+    const clamped_requests<float> own = {x, zs, ny, y0, line_lo, xlines, nslices, HALO ? (long long)xlines * PL_ROWS - 1 : pd.x_last, lane_b, edge_b};
     auto ld = [&](int zz, int l) -> f4 {
         if constexpr (HALO) {
             const int li = zz * ny + (y0 - 1 + l);                                   // uniform
@@ -139,24 +96,16 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
                 return *reinterpret_cast<const f4u *>(reinterpret_cast<const char *>(g + (long long)gl * PL_ROWS) + lane_b);
             }
         }
-        const char *p = reinterpret_cast<const char *>(x + (long long)line_of(zz, l) * PL_ROWS);
-        return *reinterpret_cast<const f4u *>(p + lane_b);
+        return own.ld(zz, l);
     };
     auto edge = [&](int zz, int l) -> float {
         if constexpr (HALO) {
             const int li = zz * ny + (y0 - 1 + l);
             if (li < line_lo || li >= xlines) return 0.0f;                           // the +-1 neighbours inside a ghost line: no row of this device has them
         }
-        long long i = (long long)line_of(zz, l) * PL_ROWS + (edge_b >> 2);
-        const long long a = (long long)line_lo * PL_ROWS;
-        i = i < a ? a : i; i = i > x_last ? x_last : i;
-        return x[i];
+        return own.edge(zz, l);
     };
-    auto yold = [&](int zz, int l) -> f4 {
-        int li = zz * ny + (y0 + l);
-        li = li < line_lo ? line_lo : li; li = li >= nslices ? nslices - 1 : li;
-        return *reinterpret_cast<const f4u *>(reinterpret_cast<const char *>(zs + (long long)li * PL_ROWS) + lane_b);
-    };
+    auto yold = [&](int zz, int l) -> f4 { return own.yold(zz, l); };
 
     // ---- the registers of the walk (walk.hpp), filled for plane z ----
     f4 Cs[4][TY], Hs[2][2], Yo[TY];
@@ -169,13 +118,7 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ZM == 1 ? zs : x) + ((long long)z_first * ny + y0) * PL_ROWS, 0, -1, 0x00020000);
     fill_registers<ZM>(Cs, Hs, Es, Yo, z, true, ld, edge, yold);
 
-    // fast steps need nothing clamped: planes up to z + 3 inside x, both lines inside y
-    int zh = zend;
-    {
-        const int a = (xlines - 1 - TY - y0) / ny - 3, bb = (nslices - TY - y0) / ny - (ZM == 1 ? 1 : 0);
-        if (xlines - 1 - TY - y0 < 0 || nslices - TY - y0 < 0) zh = 0;
-        else { zh = zh < a + 1 ? zh : a + 1; zh = zh < bb + 1 ? zh : bb + 1; }
-    }
+    const int zh = fast_limit(zend, ny, y0, TY, xlines, nslices, ZM == 1);
 
     while (z < zend) {
         unsigned long long use_hot[TY];
@@ -219,15 +162,7 @@ void plane32_walk(const float *__restrict__ x, float *__restrict__ y, float alph
         for (int l = 0; l < TY; ++l) {
             const int li = z * ny + (y0 + l);
             if (li < nslices) {                                           // uniform
-                float xs[4][7], s[4] = {};
-                stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
-                const int blk = __builtin_amdgcn_readfirstlane(blocks[li]);
-                if (blk == hot) hot_sums(s, aH, mH, xs);
-                else {
-                    if (blk != other) { bitsO = decode(blk); other = blk; }
-                    other_sums(s, s_other, t, bitsO, xs);
-                }
-                const f4 o = add_addend<ZM>(alpha, s, beta, Yo[l], Cs[1][l]);
+                const f4 o = line_result<ZM>(terms, __builtin_amdgcn_readfirstlane(blocks[li]), decode, Cs, Hs, Es, Yo, l);
                 *reinterpret_cast<f4u *>(reinterpret_cast<char *>(y + (long long)li * PL_ROWS) + lane_b) = o;
             }
         }

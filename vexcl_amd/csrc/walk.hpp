@@ -123,6 +123,35 @@ __device__ __forceinline__ VEC add_addend(V alpha, const V (&s)[R], V beta, cons
     }
     return o;
 }
+// What the result of a line needs beside x: the hot class / block in registers, one other class in s_other (which one, and its validity
+// bits: they change under a walk's slow steps), the scale and the addend.  The walks keep the arrays.
+template <typename V, int ROWS, int LANES>
+struct line_terms {
+    static constexpr int R = rows_of<V>;
+    const V (&aH)[7][R];
+    const unsigned long long (&mH)[7][R];
+    const V (&s_other)[ROWS][LANES];
+    const int hot;
+    int &other;
+    unsigned &bitsO;
+    const int t;
+    const V alpha, beta;
+};
+// The line of a slow step, the lane's vector to store: its class is the hot one, the other one, or becomes the other one now (`decode`
+// fills s_other).  (The class is decided behind the stencil, as the walks had it: decided in front of it, the fp64 kernels allocate otherwise.)
+template <int ZM, int TY, typename V, int ROWS, int LANES, typename VEC, typename DECODE>
+__device__ __forceinline__ VEC line_result(const line_terms<V, ROWS, LANES> &terms, int cls, DECODE &&decode,
+        const VEC (&Cs)[4][TY], const VEC (&Hs)[2][2], const V (&Es)[2][TY], const VEC (&Yo)[TY], int l) {
+    constexpr int R = rows_of<V>;
+    V xs[R][7], s[R] = {};
+    stencil_x(Cs[0], Cs[1], Cs[2], Hs[0], Es[0], l, xs);
+    if (cls == terms.hot) hot_sums(s, terms.aH, terms.mH, xs);
+    else {
+        if (cls != terms.other) { terms.bitsO = decode(cls); terms.other = cls; }
+        other_sums(s, terms.s_other, terms.t, terms.bitsO, xs);
+    }
+    return add_addend<ZM>(terms.alpha, s, terms.beta, Yo[l], Cs[1][l]);
+}
 
 // ---- the look-ahead: how many of the planes z, z + 1, ... (<= 64, below zh) can take fast steps ----
 // One look at the classes (blocks[] / line_class[]) of the tile's nl live lines, line0 = that of its first line in plane 0: a plane
